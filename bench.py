@@ -13,8 +13,17 @@ own B = 8192 batch and the in-batch negatives are global (N*B items per user): w
 in the batch, whole-job pairs/s = N*B*steps / time.
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the Adam table sweep, HBM
-bound, timed live with HIP events on its own stream) and `cpu_baseline` (the CPU oracle
-oracle/cpu_ref.py -- kind "port" -- timed on this box's host cores, N = 1 only).
+bound, timed live with HIP events on its own stream) and `cpu_baseline` (null in a plain run).
+A plain run sets up, warms up, times --steps steps and prints the line.  `--full` adds what takes
+runs of its own: `cpu_baseline` (the CPU oracle oracle/cpu_ref.py -- kind "port" -- timed on this
+box's host cores, N = 1 only), the HBM copy calibration beside the roofline, and the default P
+line's `secondary` (other configs, schedules and precisions).
+
+    python bench.py --full
+    python bench.py --steps 20 --warmup 5 --dump-outputs bench_outputs
+
+`--dump-outputs DIR` writes what the last timed step computed (loss, parameters and Adam moments;
+tables as a fixed, seeded sample of rows) as DIR/<name>.npy; the inputs depend on the arguments only.
 """
 from __future__ import annotations
 
@@ -349,6 +358,64 @@ def cpu_baseline_mips(corpus_cpu, K, n_queries=64):
                       f"{threads} threads, {dt:.1f} s"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_TABLE_ROWS = 4096  # per table: up to this many of the rows the last step looked up + as many seeded uniform rows
+
+
+def _table_rows_sample(p, looked_up, seed=20240611):
+    """The rows of table `p` --dump-outputs writes: the first DUMP_TABLE_ROWS ids the last step looked up and DUMP_TABLE_ROWS
+    uniform ids from a fixed seed, sorted and unique; of a row-sharded block only the rows it holds.  Returns (global row ids,
+    rows of `p`), both on the CPU."""
+    from two_tower_models_amd import parallel
+    sh = parallel.shard_of(p)
+    lo, hi = (sh.lo, sh.hi) if sh is not None else (0, p.shape[0])
+    n_rows = sh.n_rows if sh is not None else p.shape[0]
+    ids = [torch.randint(0, n_rows, (DUMP_TABLE_ROWS,), generator=torch.Generator().manual_seed(seed))]
+    if looked_up:
+        ids.append(torch.cat([t.reshape(-1).to("cpu", torch.int64) for t in looked_up])[:DUMP_TABLE_ROWS])
+    rows = torch.unique(torch.cat(ids))
+    rows = rows[(rows >= lo) & (rows < hi)]
+    return rows, rows - lo
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as <path>/<name>.npy: float64 stays float64, everything else becomes float32 (integer ids as
+    float64, exact below 2^53).  Refuses more than DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach().to("cpu")
+        exact = t.dtype == torch.float64 or not (t.is_floating_point() or t.is_complex())
+        out[name] = t.to(torch.float64 if exact else torch.float32).numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total / 2**20:.1f} MB > {DUMP_LIMIT_BYTES >> 20} MB")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def train_outputs(model, opt, last):
+    """What a caller of the train step holds after the last one: its loss, every parameter and its Adam moments (tables:
+    the rows of _table_rows_sample, their global ids under rows.<table>)."""
+    arrays = {"loss": last["loss"]}
+    b = last["batch"]
+    plan = model._lookup_plan(b[0], b[2], b[3])
+    for name, p in model.named_parameters():
+        take = lambda t: t  # noqa: E731
+        if getattr(p, "_tt_is_table", False):
+            rows, local = _table_rows_sample(p, plan.get(p))
+            arrays["rows." + name] = rows
+            idx = local.to(p.device)
+            take = lambda t, idx=idx: t.index_select(0, idx)  # noqa: E731
+        arrays["param." + name] = take(p.detach())
+        st = opt.state.get(p, {}) if opt is not None else {}
+        for key in ("exp_avg", "exp_avg_sq"):
+            if key in st:
+                arrays[f"{key}.{name}"] = take(st[key])
+    return arrays
+
+
 def build_sharded(cfg, device, rank):
     """The workload's model as THIS rank's member of a row-sharded group (parallel.row_sharded: each table's block is
     born on its owner, never whole) + its optimiser; replicated parameters are rank 0's."""
@@ -361,8 +428,9 @@ def build_sharded(cfg, device, rank):
     return model, opt
 
 
-def sharded_step_fn(model, opt, total_loss, watchdog=None):
-    """The reference loop body (ref:train/train.py:112-125) + the announcement of the NEXT batch's lookups."""
+def sharded_step_fn(model, opt, total_loss, watchdog=None, last=None):
+    """The reference loop body (ref:train/train.py:112-125) + the announcement of the NEXT batch's lookups.
+    `last` (a dict) receives the latest step's loss and batch."""
     from two_tower_models_amd import parallel
 
     def step(batch, nxt=None):
@@ -372,7 +440,10 @@ def sharded_step_fn(model, opt, total_loss, watchdog=None):
         opt.zero_grad()
         loss.backward()
         opt.step()
-        total_loss.add_(loss.detach())
+        loss = loss.detach()
+        total_loss.add_(loss)
+        if last is not None:
+            last.update(loss=loss, batch=batch)
         if watchdog is not None:
             watchdog.mark()
 
@@ -841,7 +912,7 @@ def timed_c5(cfg, device, world, rank, steps, warmup, sharded, comm_timing=True)
         collectives.comm_timing(True)
     t0 = time.perf_counter()
     for i in range(steps):
-        step(warmup + i)
+        top = step(warmup + i)
     barrier()
     dt = time.perf_counter() - t0
     comm_ms = collectives.comm_timing_summary(steps) if (sharded and comm_timing) else None
@@ -867,7 +938,8 @@ def timed_c5(cfg, device, world, rank, steps, warmup, sharded, comm_timing=True)
                                    "pipe at this box's power budget, 0.58-0.66 of the 2.5 PF spec figure on this class of box)"}
     return {"seconds": dt, "ms_per_call": dt / steps * 1e3, "roofline": roof, "comm_ms": comm_ms,
             "comm_bytes": dict(parallel.comm_bytes), "corpus_rows_this_rank": rows_local, "queries_scored_per_call_this_rank": n_q,
-            "corpus_dtype": str(model.mips_module.corpus.dtype).replace("torch.", ""), "model": model}
+            "corpus_dtype": str(model.mips_module.corpus.dtype).replace("torch.", ""), "model": model,
+            "top": top}  # the last timed call's top-K ids
 
 
 def self_launch(n: int) -> int:
@@ -918,6 +990,9 @@ def main_c5(args, cfg, device, world, rank, dist_backend, use_sharded):
             ident = rccl_identity(device, world)
     rec = timed_c5(cfg, device, world, rank, args.steps, args.warmup, use_sharded)
     rec.pop("model")
+    top = rec.pop("top")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"top_k_ids": top})
     dt = rec["seconds"]
     rank_ms = None
     if world > 1:
@@ -965,10 +1040,17 @@ def main():
     ap.add_argument("--workload", default="P", choices=sorted(WORKLOADS),
                     help="P: the headline train step.  C5: BASELINE config 5's inference (queries/s of model.forward() -> top-1000 of "
                          "a 10 M-row bf16 corpus; --gpus N row-shards tables and corpus)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the CPU baseline, the HBM copy calibration of the roofline and, for the "
+                         "default single-GPU P run, the `secondary` object (off: the line carries the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` object (C2 / C3 / deferred-Adam train steps, config 5 MIPS) the default "
-                         "single-GPU P run appends")
+                    help="with --full: skip the `secondary` object (C2 / C3 / deferred-Adam train steps, config 5 MIPS) the "
+                         "default single-GPU P run appends")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: loss, parameters, Adam moments; tables as a fixed, seeded sample of rows).  "
+                         "Single-GPU runs then spin up for the full 12 blocks, so the outputs depend on the arguments only")
     ap.add_argument("--overlap", default="forward", choices=["forward", "zero_grad", "off"],
                     help="when DenseExactAdam starts the table sweep (optim.py); all three are bit-identical")
     ap.add_argument("--sharded", action="store_true", help="use the row-sharded module path even at --gpus 1")
@@ -1047,7 +1129,8 @@ def main():
         model, opt = build_sharded(cfg, device, rank)  # cfg['model'] selects base / hist / debias
         batches = make_batches(cfg, 16, device, seed=1234 + 1000 * rank)
         total_loss = torch.zeros((), device=device)
-        step = sharded_step_fn(model, opt, total_loss, watchdog)
+        last = {}  # the latest step's loss and batch (--dump-outputs)
+        step = sharded_step_fn(model, opt, total_loss, watchdog, last)
     else:
         model = build_model(cfg, device)
         opt = A.DenseExactAdam(model.parameters(), lr=1e-3, overlap_sweep=args.overlap, lazy=args.adam == "lazy")
@@ -1068,6 +1151,7 @@ def main():
             return b
 
         pending = {}
+        last = {}  # the latest step's loss and batch (--dump-outputs)
 
         def step(batch, nxt=None):
             if args.fresh_ids:
@@ -1076,7 +1160,9 @@ def main():
                     nxt = pending["next"] = refresh(nxt)
             if args.phase == "fwd":
                 with torch.no_grad():
-                    total_loss.add_(model.train_forward(*batch))
+                    loss = model.train_forward(*batch)
+                total_loss.add_(loss)
+                last.update(loss=loss, batch=batch)
                 return
             loss = model.train_forward(*batch)
             if args.adam == "lazy" and nxt is not None:  # replay the next batch's rows underneath this step
@@ -1088,7 +1174,9 @@ def main():
             else:
                 for p in opt._tables:  # step() would have consumed these
                     p._tt_lookups.clear()
-            total_loss.add_(loss.detach())  # the loop's loss accumulation, without the host sync
+            loss = loss.detach()
+            total_loss.add_(loss)  # the loop's loss accumulation, without the host sync
+            last.update(loss=loss, batch=batch)
 
     if args.graph:
         if use_sharded or args.phase != "step":
@@ -1096,7 +1184,9 @@ def main():
         graphed = A.GraphedTrainStep(model, opt, batches[0], warmup=2)
 
         def step(batch):  # noqa: F811 -- replaces the eager step
-            total_loss.add_(graphed(*batch))
+            loss = graphed(*batch)  # (the graph's static output: holds the latest replay's loss)
+            total_loss.add_(loss)
+            last.update(loss=loss, batch=batch)
 
     def barrier():
         if world > 1:
@@ -1115,7 +1205,7 @@ def main():
     # at most 12 blocks.  The first process on a box that has sat idle runs its first second(s) of GPU work at a lower
     # memory clock: the same binary measured 5.77 / 5.93 ms in a window starting 0.3 s into the process and 5.39 / 5.44
     # ms for the same shape half a minute later in the same process (round 5).
-    spun, last, spin_blocks_ms = 0, None, []
+    spun, prev_blk, spin_blocks_ms = 0, None, []
     while args.spinup > 0 and spun < 12 * args.spinup:
         torch.cuda.synchronize()
         t_blk = time.perf_counter()
@@ -1125,10 +1215,12 @@ def main():
         t_blk = time.perf_counter() - t_blk
         spun += args.spinup
         spin_blocks_ms.append(round(t_blk / args.spinup * 1e3, 4))  # -> the line's `spinup_ms_per_step_by_block`
-        # (N > 1: every rank must run the SAME number of steps -- the collectives pair up -- so no rank-local decision: 2 blocks)
-        if (world > 1 and spun >= 2 * args.spinup) or (world == 1 and last is not None and abs(t_blk - last) <= 0.01 * last):
+        # (N > 1: every rank must run the SAME number of steps -- the collectives pair up -- so no rank-local decision: 2 blocks.
+        # --dump-outputs: the outputs must not depend on timing either, so no early stop: all 12 blocks)
+        if (world > 1 and spun >= 2 * args.spinup) or (world == 1 and not args.dump_outputs and prev_blk is not None
+                                                       and abs(t_blk - prev_blk) <= 0.01 * prev_blk):
             break
-        last = t_blk
+        prev_blk = t_blk
     for i in range(args.warmup):
         run(i)
     barrier()
@@ -1179,6 +1271,8 @@ def main():
     ce_ms, ce_cnt = C.c_double(0.0), C.c_int64(0)
     N.check(lib.tt_profile_read(b"ce_bwd_kernel", C.byref(ce_ms), C.byref(ce_cnt)), "tt_profile_read")
     lib.tt_profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(model, opt, last))
 
     ident = rccl_identity(device, world) if (use_sharded and dist_backend == "nccl") else None
     if rank == 0:
@@ -1210,14 +1304,15 @@ def main():
                     "avg_launch_ms": round(ms.value / cnt.value, 4),
                     "algorithmic_bytes_per_launch": sweep_bytes_step * args.steps / cnt.value}
             # the box's own streaming rate, measured here and now (a copy as large as the sweep's footprint, same process, same
-            # allocator state, right after the timed steps), and the clocks on both sides of the timed region: a line whose
-            # `frac` moved can be attributed -- `frac_of_copy` moves with the code, `hbm_copy_GBps` with the box
-            try:
-                cal = hbm_copy_calibration(lib, N, device, min(sweep_bytes_step, 40e9))
-                roof.update(hbm_copy_GBps=cal["GBps"], hbm_copy_best_GBps=cal["best_GBps"],
-                            frac_of_copy=round(achieved / cal["GBps"], 4), hbm_copy=cal)
-            except Exception as e:  # noqa: BLE001
-                roof["hbm_copy_GBps"] = f"unavailable ({type(e).__name__}: {e})"
+            # allocator state, right after the timed steps; --full), and the clocks on both sides of the timed region: a line
+            # whose `frac` moved can be attributed -- `frac_of_copy` moves with the code, `hbm_copy_GBps` with the box
+            if args.full:
+                try:
+                    cal = hbm_copy_calibration(lib, N, device, min(sweep_bytes_step, 40e9))
+                    roof.update(hbm_copy_GBps=cal["GBps"], hbm_copy_best_GBps=cal["best_GBps"],
+                                frac_of_copy=round(achieved / cal["GBps"], 4), hbm_copy=cal)
+                except Exception as e:  # noqa: BLE001
+                    roof["hbm_copy_GBps"] = f"unavailable ({type(e).__name__}: {e})"
             # (before / after are read with the device idle between launches -- the shader clock may already have dropped)
             roof["clocks"] = {"before": clocks_before, "during": clocks_during, "after": clocks_after}
             roof["table_arena"] = getattr(opt, "arena_note", None)  # candidate allocations timed at the first step, the one kept
@@ -1273,13 +1368,13 @@ def main():
                                         "sweep_workgroups": opt._sweep_wgs or 768, "sweep_level_decided_by": opt.sweep_level_note()}}
             out["rank_ms_per_step"] = rank_ms  # slowest / fastest rank's own clock over the timed steps (null at N = 1)
             out["check"] = check
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         else:
             out["cpu_baseline"] = None
         default_run = (world == 1 and not use_sharded and args.workload == "P" and args.phase == "step"
                        and args.adam == "dense" and not args.graph and not args.fresh_ids)
-        if default_run and not args.no_secondary:
+        if default_run and args.full and not args.no_secondary:
             # release the headline model's 17 GB first
             model = opt = batches = step = graphed = None  # noqa: F841
             import gc

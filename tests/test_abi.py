@@ -86,7 +86,7 @@ def test_module_surface_matches_reference_names():
     assert enc.get_output_dim() == 16 and enc.positional_embeddings.shape == (6, 8)
 
 
-def test_bench_roofline_traffic_key_resolves():
+def test_bench_roofline_traffic_key_resolves(tmp_path):
     """bench.py's roofline.traffic comes from profiles/pmc_traffic.json: the key the default run looks up must exist
     (round 3 shipped a flat record and the driver's line carried `"traffic": null`), in the keyed and the flat form."""
     import importlib.util
@@ -101,9 +101,41 @@ def test_bench_roofline_traffic_key_resolves():
     alg = bench.algorithmic_sweep_bytes(bench.WORKLOADS["P"], 1)
     assert got is not None and 0.98 * alg < got < 1.10 * alg, (got, alg)
     assert bench.pmc_traffic_bytes(path, "C2", 1) is None  # no measurement committed for that workload: null, not a wrong number
-    flat = os.path.join(os.environ.get("TMPDIR", "/tmp"), "pmc_flat_test.json")
+    flat = str(tmp_path / "pmc_flat_test.json")
     json.dump(json.load(open(path))["P_gpus1"], open(flat, "w"))
     assert bench.pmc_traffic_bytes(flat, "P", 1) == got
+
+
+def test_bench_dump_outputs_sample_and_limit(tmp_path):
+    """`bench.py --dump-outputs`: a table's sample is the last step's looked-up rows plus seeded uniform rows, the same on
+    every call, restricted to the block a row-sharded table holds; the arrays land as float32 / float64 .npy files and more
+    than 64 MB in all is refused."""
+    import importlib.util
+
+    import numpy as np
+
+    from two_tower_models_amd import parallel
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    whole = torch.nn.Parameter(torch.zeros(100_000, 4))
+    ids = [torch.tensor([5, 99_999, 5, 70_000])]
+    rows, local = bench._table_rows_sample(whole, ids)
+    again, _ = bench._table_rows_sample(whole, ids)
+    assert torch.equal(rows, again) and torch.equal(rows, local) and torch.equal(rows, torch.unique(rows))
+    assert {5, 99_999, 70_000} <= set(rows.tolist()) and len(rows) <= 4 + bench.DUMP_TABLE_ROWS
+    block = torch.nn.Parameter(torch.zeros(50_000, 4))
+    block._tt_shard = parallel.RowShard(100_000, 4, 2, 1)  # rows [50 000, 100 000)
+    brows, blocal = bench._table_rows_sample(block, ids)
+    assert torch.equal(brows, rows[rows >= 50_000]) and torch.equal(blocal, brows - 50_000)
+    bench.dump_outputs(str(tmp_path / "d"), {"loss": torch.tensor(0.5), "ids": torch.arange(3),
+                                             "w": torch.ones(2, 2, dtype=torch.bfloat16)})
+    got = {n: np.load(tmp_path / "d" / n) for n in sorted(os.listdir(tmp_path / "d"))}
+    assert {n: a.dtype for n, a in got.items()} == {"ids.npy": np.float64, "loss.npy": np.float32, "w.npy": np.float32}
+    assert got["ids.npy"].tolist() == [0.0, 1.0, 2.0] and float(got["loss.npy"]) == 0.5
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(17 << 20)})
+    assert not os.path.exists(tmp_path / "big")
 
 
 def test_reference_package_name_resolves_to_this_implementation():

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -43,6 +44,35 @@ def test_single_gpu_line():
     assert roof["bound"] == "hbm" and roof["unit"] == "GB/s" and roof["launches"] == 3  # one sweep launch per step covers both tables
     assert abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-3
     assert "workload" in out["config"] and "model" not in out["config"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run carries the headline only (no `--full` figures) and times exactly --steps steps.  `--dump-outputs DIR`
+    writes the last timed step's loss, parameters and Adam moments (table rows: a fixed sample) as float32 / float64 .npy
+    files, at most 64 MB; two runs with the same arguments write the same arrays."""
+    def run(d):
+        r = subprocess.run([sys.executable, "bench.py", "--workload", "tiny", "--steps", "4", "--warmup", "2", "--spinup", "5",
+                            "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600,
+                           stdin=subprocess.DEVNULL)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return _last_json(r.stdout)
+    out = run(tmp_path / "a")
+    run(tmp_path / "b")
+    assert KEYS <= set(out) and out["steps"] == 4 and out["roofline"]["launches"] == 4
+    assert out["spinup_steps"] == 12 * 5  # no timing-dependent early stop when the outputs are dumped
+    assert out["cpu_baseline"] is None and "secondary" not in out and "hbm_copy_GBps" not in out["roofline"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "param.item_id_embedding_arch.weight.npy", "exp_avg_sq.user_id_embedding_arch.weight.npy",
+            "param.user_tower_arch.weight.npy", "exp_avg.user_tower_arch.weight.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, n
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-7, err_msg=n)
+        total += a.nbytes
+    assert 0 < total <= 64 << 20
+    assert np.isfinite(np.load(tmp_path / "a" / "loss.npy")).all()
 
 
 def test_two_rank_launch_line():
@@ -87,13 +117,15 @@ def test_self_launch_needs_no_env():
 
 def test_sharded_module_path_at_world1_matches_the_single_gpu_headline():
     """`bench.py --sharded --gpus 1` (the row-sharded module path over an RCCL group of one: the N = 1 point a scaling run starts
-    from) against the module-path headline `bench.py` on the same box, same P shapes, back to back: within 5 %
+    from) against the module-path headline `bench.py` on the same box, same P shapes, back to back, both with `--full` for the
+    HBM copy calibration: within 5 %
     (round-4 measurements: 0.97-1.03 on five boxes; the two paths launch the same sweep / logits / tower kernels and
     differ in the routing kernels of the sharded lookups).  The multi-rank line's `comm` record carries per-exchange
     times and the step schedule."""
     def run(extra):
-        r = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-secondary", "--steps", "20", "--warmup",
-                            "10", *extra], cwd=ROOT, capture_output=True, text=True, timeout=900, stdin=subprocess.DEVNULL)
+        r = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-secondary", "--steps", "20",
+                            "--warmup", "10", *extra], cwd=ROOT, capture_output=True, text=True, timeout=900,
+                           stdin=subprocess.DEVNULL)
         assert r.returncode == 0, r.stderr[-2000:]
         return _last_json(r.stdout)
     mod = run([])
