@@ -365,38 +365,27 @@ __global__ __launch_bounds__(256) void adam_finish_tables_kernel(const FinishJob
 // lasts (a one-shot grid lets the dispatcher refill every freed slot with another small sweep workgroup, and a
 // 256-VGPR / 64-KiB workgroup never finds a whole CU's worth of room: sweep + compute in series).
 typedef float vf4 __attribute__((ext_vector_type(4)));
-template <bool NT>
 __device__ __forceinline__ float4 sweep_load(const float4* p) {
-  if constexpr (NT) {
-    const vf4 t = __builtin_nontemporal_load(reinterpret_cast<const vf4*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-  } else {
-    return *p;
-  }
+  const vf4 t = __builtin_nontemporal_load(reinterpret_cast<const vf4*>(p));
+  return make_float4(t.x, t.y, t.z, t.w);
 }
-template <bool NT>
 __device__ __forceinline__ void sweep_store(const float4& v, float4* p) {
-  if constexpr (NT) {
-    vf4 t;
-    t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-    __builtin_nontemporal_store(t, reinterpret_cast<vf4*>(p));
-  } else {
-    *p = v;
-  }
+  vf4 t;
+  t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+  __builtin_nontemporal_store(t, reinterpret_cast<vf4*>(p));
 }
 
-// NT: non-temporal loads AND stores (every byte is touched exactly once per step, nothing is worth keeping in
+// Non-temporal loads AND stores (every byte is touched exactly once per step, nothing is worth keeping in
 // L2 / MALL).  Measured with tools/sweep_probe.hip, all variants in one process on the same buffers: nt on both
 // sides +4 % at 3 workgroups per CU, +9.5 % at 2 per CU (6.16 vs 5.62 TB/s on a slower box, 6.33 vs 6.10 on a
 // faster one); nt on the loads alone +1.5 %, on the stores alone -3 %.  (Round 1 tried nt on the one-shot grid
 // form only, where it lost.)  FEWER resident sweep waves stream better, not worse: 1-2 workgroups per CU beat 3,
 // 4, 6, 8 -- fewer DRAM pages open at once -- as long as each lane keeps 12 x 16 B in flight.
-template <int ITERS, int UNR, bool NT>
+template <int ITERS, int UNR>
 __global__ __launch_bounds__(256) void adam_sweep_persistent_kernel(float4* __restrict__ W, float4* __restrict__ M,
                                                                     float4* __restrict__ V, int64_t n4,
                                                                     const double* __restrict__ hyper,
-                                                                    unsigned* __restrict__ ctr, int prio) {
-  if (prio) __builtin_amdgcn_s_setprio(3);  // A/B (TT_SWEEP_PRIO): the sweep's waves win instruction issue on their SIMD
+                                                                    unsigned* __restrict__ ctr) {
   const AdamConst c = load_hyper(hyper);
   const unsigned n_chunks = (unsigned)((n4 + 256 * ITERS - 1) / (256 * ITERS));
   __shared__ unsigned s_next[2];
@@ -416,12 +405,12 @@ __global__ __launch_bounds__(256) void adam_sweep_persistent_kernel(float4* __re
     for (int k = 0; k < ITERS; ++k) {
       const int64_t i = base + (int64_t)k * 256;
       if (i >= n4) break;
-      float4 p = sweep_load<NT>(W + i), m = sweep_load<NT>(M + i), v = sweep_load<NT>(V + i);
+      float4 p = sweep_load(W + i), m = sweep_load(M + i), v = sweep_load(V + i);
       adam_elem_zero_grad(p.x, m.x, v.x, c);
       adam_elem_zero_grad(p.y, m.y, v.y, c);
       adam_elem_zero_grad(p.z, m.z, v.z, c);
       adam_elem_zero_grad(p.w, m.w, v.w, c);
-      sweep_store<NT>(p, W + i); sweep_store<NT>(m, M + i); sweep_store<NT>(v, V + i);
+      sweep_store(p, W + i); sweep_store(m, M + i); sweep_store(v, V + i);
     }
     __syncthreads();
     par ^= 1;
@@ -447,10 +436,9 @@ struct SweepTables {
   unsigned first_chunk[SWEEP_MAX_TABLES + 1];  // table t owns chunks [first_chunk[t], first_chunk[t + 1])
   int n;
 };
-template <int ITERS, int UNR, bool NT>
+template <int ITERS, int UNR>
 __global__ __launch_bounds__(256) void adam_sweep_tables_kernel(const SweepTables tabs, const double* __restrict__ hyper,
-                                                                unsigned* __restrict__ ctr, int prio) {
-  if (prio) __builtin_amdgcn_s_setprio(3);
+                                                                unsigned* __restrict__ ctr) {
   const AdamConst c = load_hyper(hyper);
   const unsigned n_chunks = tabs.first_chunk[tabs.n];
   __shared__ unsigned s_next[2];
@@ -473,12 +461,12 @@ __global__ __launch_bounds__(256) void adam_sweep_tables_kernel(const SweepTable
     for (int k = 0; k < ITERS; ++k) {
       const int64_t i = base + (int64_t)k * 256;
       if (i >= n4) break;
-      float4 p = sweep_load<NT>(W + i), m = sweep_load<NT>(M + i), v = sweep_load<NT>(V + i);
+      float4 p = sweep_load(W + i), m = sweep_load(M + i), v = sweep_load(V + i);
       adam_elem_zero_grad(p.x, m.x, v.x, c);
       adam_elem_zero_grad(p.y, m.y, v.y, c);
       adam_elem_zero_grad(p.z, m.z, v.z, c);
       adam_elem_zero_grad(p.w, m.w, v.w, c);
-      sweep_store<NT>(p, W + i); sweep_store<NT>(m, M + i); sweep_store<NT>(v, V + i);
+      sweep_store(p, W + i); sweep_store(m, M + i); sweep_store(v, V + i);
     }
     __syncthreads();
     par ^= 1;
@@ -507,7 +495,7 @@ struct SweepTablesMarked {
   const unsigned* marks[SWEEP_MAX_TABLES];
   int sh[SWEEP_MAX_TABLES];
 };
-template <int ITERS, int PAIR, bool NT>
+template <int ITERS, int PAIR>
 __global__ __launch_bounds__(256) void adam_sweep_tables_marked_kernel(const SweepTablesMarked tm, const double* __restrict__ hyper,
                                                                        unsigned* __restrict__ ctr) {
   const AdamConst c = load_hyper(hyper);
@@ -559,7 +547,7 @@ __global__ __launch_bounds__(256) void adam_sweep_tables_marked_kernel(const Swe
 #pragma unroll
       for (int q = 0; q < PAIR; ++q) {
         const int64_t i = base + (int64_t)(k + q) * 256;
-        if (live[q]) { p[q] = sweep_load<NT>(W + i); m[q] = sweep_load<NT>(M + i); v[q] = sweep_load<NT>(V + i); }
+        if (live[q]) { p[q] = sweep_load(W + i); m[q] = sweep_load(M + i); v[q] = sweep_load(V + i); }
       }
 #pragma unroll
       for (int q = 0; q < PAIR; ++q) {
@@ -569,7 +557,7 @@ __global__ __launch_bounds__(256) void adam_sweep_tables_marked_kernel(const Swe
           adam_elem_zero_grad(p[q].y, m[q].y, v[q].y, c);
           adam_elem_zero_grad(p[q].z, m[q].z, v[q].z, c);
           adam_elem_zero_grad(p[q].w, m[q].w, v[q].w, c);
-          sweep_store<NT>(p[q], W + i); sweep_store<NT>(m[q], M + i); sweep_store<NT>(v[q], V + i);
+          sweep_store(p[q], W + i); sweep_store(m[q], M + i); sweep_store(v[q], V + i);
         }
       }
     }
@@ -803,7 +791,7 @@ static int device_cu_count() {
   return cached[dev];
 }
 
-// n_wgs > 0: upper limit of persistent workgroups (the caller's sweep throttle; 0 = TT_SWEEP_PERSIST per CU)
+// n_wgs > 0: upper limit of persistent workgroups (the caller's sweep throttle; 0 = SWEEP_DEFAULT_PERSIST per CU)
 static int launch_sweep(float* W, float* M, float* V, int64_t n_rows, int64_t dim, const double* hyper,
                         hipStream_t st, int n_wgs = 0) {
   int rc;
@@ -822,7 +810,7 @@ static int launch_sweep(float* W, float* M, float* V, int64_t n_rows, int64_t di
     unsigned* ctr = reinterpret_cast<unsigned*>(const_cast<double*>(hyper) + 7);
     unsigned grid = (unsigned)(device_cu_count() * SWEEP_DEFAULT_PERSIST);
     if (n_wgs > 0 && (unsigned)n_wgs < grid) grid = (unsigned)n_wgs;
-    adam_sweep_persistent_kernel<4, 4, true><<<grid, 256, 0, st>>>(w4, m4, v4, n4, hyper, ctr, 0);
+    adam_sweep_persistent_kernel<4, 4><<<grid, 256, 0, st>>>(w4, m4, v4, n4, hyper, ctr);
     if ((rc = check_launch("adam_sweep_kernel"))) return rc;
   }
   if (n4 * 4 < total) {
@@ -983,7 +971,7 @@ extern "C" int tt_adam_tables_sweep(const tt_adam_tensor* tables, int32_t n_tabl
   unsigned grid = (unsigned)(device_cu_count() * SWEEP_DEFAULT_PERSIST);
   if (want > 0 && (unsigned)want < grid) grid = (unsigned)want;
   ProfScope prof("adam_sweep_kernel", st);
-  adam_sweep_tables_kernel<4, 4, true><<<grid, 256, 0, st>>>(tabs, hyper, ctr, 0);
+  adam_sweep_tables_kernel<4, 4><<<grid, 256, 0, st>>>(tabs, hyper, ctr);
   return check_launch("adam_sweep_tables_kernel");
 }
 
@@ -1041,7 +1029,7 @@ extern "C" int tt_adam_tables_sweep_marked(const tt_adam_tensor* tables, const i
   ProfScope prof("adam_sweep_kernel", st);
   // two row triples in flight per wave: 62 registers (see the kernel); one at a time (46) 3.27 ms per C3 step at its best
   // width (384 workgroups), two 3.09 (256), four (92 registers) 3.34 (128) -- one process each, profiles/r06_marked_sweep_AB.txt
-  adam_sweep_tables_marked_kernel<4, 2, true><<<grid, 256, 0, st>>>(tm, hyper, ctr);
+  adam_sweep_tables_marked_kernel<4, 2><<<grid, 256, 0, st>>>(tm, hyper, ctr);
   return check_launch("adam_sweep_tables_marked_kernel");
 }
 
@@ -1269,12 +1257,12 @@ __global__ __launch_bounds__(256) void stream_copy_kernel(const float4* __restri
 #pragma unroll
   for (int k = 0; k < ITERS; ++k) {
     const int64_t i = base + (int64_t)k * 256;
-    if (i < n4) v[k] = sweep_load<true>(src + i);
+    if (i < n4) v[k] = sweep_load(src + i);
   }
 #pragma unroll
   for (int k = 0; k < ITERS; ++k) {
     const int64_t i = base + (int64_t)k * 256;
-    if (i < n4) sweep_store<true>(v[k], dst + i);
+    if (i < n4) sweep_store(v[k], dst + i);
   }
 }
 }  // namespace tt

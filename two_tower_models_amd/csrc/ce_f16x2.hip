@@ -25,13 +25,6 @@
 // Shapes: D = 128, M a multiple of 256, N of 1024.
 #include "common.hpp"
 
-// measurement variants (tools/ce16_variants.sh; results are WRONG by design): 1 no logits stores, 2 no E product, 4 non-temporal
-// logits stores [correct],
-// 8 the tile wait leaves four vector-memory instructions (the logits stores) in flight, 32 backward without the logits loads
-#ifndef TT_CE16_EXP
-#define TT_CE16_EXP 0
-#endif
-
 namespace tt {
 namespace {
 
@@ -225,10 +218,8 @@ __device__ __forceinline__ void fwd_tile(const FwdStage* st, const u32x4 (&uh)[8
       ih[(t + 1) & 1] = *reinterpret_cast<const u32x4*>(rowh + off);
       il[(t + 1) & 1] = *reinterpret_cast<const u32x4*>(rowl + off);
     }
-#if !(TT_CE16_EXP & 128)
     __builtin_amdgcn_sched_barrier(0);  // the reads of step t + 1 go out BEFORE step t's MFMAs (else hipcc reuses ih's registers
                                         // and issues the read one MFMA ahead of its use: an LDS latency per k-step)
-#endif
     acc = MFMA16(ih[t & 1], uh[t], acc);
     acc = MFMA16(ih[t & 1], ul[t], acc);
     acc = MFMA16(il[t & 1], uh[t], acc);
@@ -243,34 +234,13 @@ __device__ __forceinline__ void fwd_tile(const FwdStage* st, const u32x4 (&uh)[8
     v[e] = acc[e] * out_scale;
     tmax = fmaxf(tmax, v[e]);
   }
-#if !(TT_CE16_EXP & 1)
   if (logit_row)  // (wave-uniform: null = the caller keeps no logits, tt_ce16_bwd_recompute forms them again)
-#if TT_CE16_EXP & (4 | 16 | 256)
-  {  // the wave's 32 x 32 tile is one contiguous 4 KiB block of the logits buffer, row-major inside (see tt_hotpath.h)
-    float* tile = logit_row + (item0 >> 5) * 1024 + 8 * 0 + 4 * h;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      typedef float f32x4 __attribute__((ext_vector_type(4)));
-      const f32x4 q = {v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
-#if TT_CE16_EXP & 4
-      __builtin_nontemporal_store(q, reinterpret_cast<f32x4*>(tile + 8 * g));
-#else
-      // (plain stores: non-temporal ones were measured 25 % slower here -- 1.30 vs 1.04 ms, WRITE_SIZE 3.1 GB for 2.15 GB of
-      // logits: the 32-byte pieces of a line no longer merge in L2)
-#if TT_CE16_EXP & 16  // (measurement: the same bytes as four fully coalesced 1-KiB stores, WRONG layout)
-      *reinterpret_cast<f32x4*>(logit_row - r * 32 + (item0 >> 5) * 1024 + g * 256 + (h * 32 + r) * 4) = q;
-#else
-      *reinterpret_cast<f32x4*>(tile + 8 * g) = q;
-#endif
-#endif
-    }
-  }
-#else
   {  // The wave's 32 x 32 tile is one contiguous 4 KiB block of the logits buffer, row-major inside (see tt_hotpath.h).  Straight
      // from the score registers (lane = user) a store instruction would write 32 bytes into each of 32 rows -- 8.5 % of the kernel
-     // (variant 16) -- so the tile is turned through the wave's own 4-KiB LDS slice: written as [user][item] with the 16-byte
-     // chunks of a row XOR-swizzled by the row (conflict-free both ways), read back 8 lanes per row, stored as four fully
-     // coalesced 1-KiB pieces.  One wave, LDS in order: no barrier.
+     // -- so the tile is turned through the wave's own 4-KiB LDS slice: written as [user][item] with the 16-byte chunks of a row
+     // XOR-swizzled by the row (conflict-free both ways), read back 8 lanes per row, stored as four fully coalesced 1-KiB
+     // pieces.  One wave, LDS in order: no barrier.  (Plain stores: non-temporal ones of the 32-byte pieces were measured 25 %
+     // slower, 1.30 vs 1.04 ms, WRITE_SIZE 3.1 GB for 2.15 GB of logits -- the pieces of a line no longer merge in L2.)
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int lane = h * 32 + r;
 #pragma unroll
@@ -284,8 +254,6 @@ __device__ __forceinline__ void fwd_tile(const FwdStage* st, const u32x4 (&uh)[8
     for (int g = 0; g < 4; ++g)  // rows 8 g + (lane >> 3), chunk lane & 7
       *reinterpret_cast<f32x4*>(tile + g * 256) = *reinterpret_cast<const f32x4*>(src + g * 1024);
   }
-#endif
-#endif
   tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
   if (tmax > mx) {  // (lane-divergent, rare after the first tiles)
     const float f = __builtin_amdgcn_exp2f(mx - tmax);
@@ -309,25 +277,6 @@ __device__ __forceinline__ void fwd_tile(const FwdStage* st, const u32x4 (&uh)[8
     split8(pv, ph[s], pl[s]);
   }
   // E^T[d][user] += I^T[d][item] P[item][user]: A = the tile's transposed image, B = the probabilities just formed
-#if TT_CE16_EXP & 2
-  E[0][0] += __builtin_bit_cast(float, ph[0][0] ^ pl[1][3]);
-  return;
-#endif
-#if TT_CE16_EXP & 128
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int at = s * 4096 + h * 2048 + (b * 32 + r) * 16;
-      const u32x4 th = *reinterpret_cast<const u32x4*>(st->tr_h + at);
-      const u32x4 tl = *reinterpret_cast<const u32x4*>(st->tr_l + at);
-      E[b] = MFMA16(th, ph[s], E[b]);
-      E[b] = MFMA16(th, pl[s], E[b]);
-      E[b] = MFMA16(tl, ph[s], E[b]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#else
   // the eight (s, b) fragment pairs, each read one pair ahead of its three MFMAs
   u32x4 th[2], tl[2];
   {
@@ -349,16 +298,11 @@ __device__ __forceinline__ void fwd_tile(const FwdStage* st, const u32x4 (&uh)[8
     E[b] = MFMA16(tl[i & 1], ph[s], E[b]);
     __builtin_amdgcn_sched_barrier(0x6);
   }
-#endif
 }
 
 }  // namespace
 
-#if TT_CE16_EXP & 8
-#define C16_FWD_WAIT 0x0f74
-#else
 #define C16_FWD_WAIT 0x0f70
-#endif
 __global__ __launch_bounds__(64 * C16_NW, 2) void ce16_fwd_kernel(const FwdArgs p) {
   __shared__ __attribute__((aligned(1024))) FwdStage ring0;
   __shared__ __attribute__((aligned(1024))) FwdStage ring1;
@@ -472,14 +416,9 @@ __device__ __forceinline__ void bwd_fetch(const BwdArgs& p, int64_t user0, int64
   // buffer loads: tile base in a scalar resource descriptor, row offset an immediate, ONE 32-bit per-lane offset
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.logits + ((user0 >> 5) * (p.N >> 5) + item_blk) * 1024), 0, 4096, 0x00020000);
-#if TT_CE16_EXP & 32
-#pragma unroll
-  for (int e = 0; e < 16; ++e) s[e] = (float)(lane_off + e) * 1e-9f;
-#else
 #pragma unroll
   for (int e = 0; e < 16; ++e)
     s[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, lane_off, ((e & 3) + 8 * (e >> 2)) * 128, 0));
-#endif
   // the tile's 32 (lse, coef) pairs: one value per lane of wave 0, handed to everybody through LDS (every lane needs 16 of
   // each; fetched per lane they would be twice the logits' load traffic and 64 registers of double buffer)
   if (wave == 0) stat = (lane < 32 ? p.row_lse : p.coef)[user0 + (lane & 31)];

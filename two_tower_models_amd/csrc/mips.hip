@@ -37,10 +37,6 @@
 #include "common.hpp"
 #include "mfma_stream.hpp"
 
-#ifndef TT_MIPS_EXP
-#define TT_MIPS_EXP 0  // measurement variants of the bf16 pass 1 (tools/mips_variants.sh); 0 = the product kernel
-#endif
-
 namespace tt {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -394,12 +390,8 @@ __device__ __forceinline__ void corpus_tile_dma(const char* __restrict__ Cm, int
   constexpr int NI = CT / RPI / 4;   // instructions per wave
   // buffer loads (see tile_dma in mfma_stream.hpp): chunk base in a scalar descriptor; rows past the end of
   // the corpus are outside the descriptor and land as zeros (the epilogue masks them)
-#if TT_MIPS_EXP & 16
-  const int64_t chunk0 = ((t >> 1) & 63) * CHUNK, left = C - chunk0;  // measurement variant: the corpus "stream" stays in L2
-#else
   // g7: 256-row chunks, this tile pair is its first / second 64 rows of each lane half
   const int64_t chunk0 = (t >> (1 + g7)) * (CHUNK << g7), left = C - chunk0;
-#endif
   const int chunk_rows = CHUNK << g7, hs = 64 << g7, pair_rows = g7 ? 64 * (int)((t >> 1) & 1) : 0;
   const int rows_here = left < chunk_rows ? (int)left : chunk_rows;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Cm + chunk0 * row_bytes), 0,
@@ -475,11 +467,7 @@ __device__ __forceinline__ void score_tile_f16x2(const float* ys, const typename
 template <int DT, int DPX, int NQ, int STAGES, int SF>
 __global__ __launch_bounds__(256, 2) void mips_pass1_dma_kernel(const MipsArgs p) {
   constexpr bool SHARE = SF != 0;
-#ifdef TT_MIPS_ROWARG  // measurement variant (tools/mips_variants.sh): the row-exact epilogue for bf16 as well
-  constexpr bool QUADS = false;
-#else
   constexpr bool QUADS = DT == TT_BF16;  // the best item of a group is tracked per 4-row quad (see the epilogue)
-#endif
   static_assert(SF == 0 || SF == 2 || SF == 4, "shared-query form: waves per query block");
   using O = Op<DT, DPX>;
   using TM = TileMap<DPX, true>;  // row bytes = 32 * DPX for both dtypes
@@ -546,11 +534,7 @@ __global__ __launch_bounds__(256, 2) void mips_pass1_dma_kernel(const MipsArgs p
   const uint32_t nq32 = (uint32_t)p.nq, lane_q = (uint32_t)qbase, lane_off = (uint32_t)h * nq32 + lane_q;
   constexpr int HALFPOS = QUADS ? 16 : 64;  // positions (quads / rows) per 64 rows
   auto store_chunk = [&](int64_t chunk) {
-#if TT_MIPS_EXP & 32
-    const int64_t base = 2 * (chunk & 7) * p.nq;  // measurement variant: the result stores stay in L2
-#else
     const int64_t base = 2 * chunk * p.nq;
-#endif
     uint32_t* const g1 = p.gmax + base;
     uint32_t* const g2 = p.gm2 + base;
     const bool second_empty = ((2 * chunk + 1) << p.gshift) >= p.C;  // only the corpus' last chunk (wave-uniform)
@@ -558,11 +542,7 @@ __global__ __launch_bounds__(256, 2) void mips_pass1_dma_kernel(const MipsArgs p
     const int pos_base = g7 ? HALFPOS : 0;
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
-#if TT_MIPS_EXP & 8
-      if (m1[n] == 12345.678f) {  // measurement variant: (practically) no result stores
-#else
       if (lane_q + 32u * n < nq32) {
-#endif
         uint32_t best = __float_as_uint(m1[n]);
         if (second_empty && h) best = 0xFFFFFFFFu;
         __builtin_nontemporal_store(best, &g1[lane_off + 32u * n]);
@@ -619,20 +599,11 @@ __global__ __launch_bounds__(256, 2) void mips_pass1_dma_kernel(const MipsArgs p
             const uint32_t a = lrow + 16u * (uint32_t)((2 * g + h) ^ sw);
             asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(a) : "memory");
           };
-#if TT_MIPS_EXP & 2
-          // measurement variant: ONE LDS read per sub-tile instead of one per k-group
           rd(yy[0], 0);
-          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(yy[0]) : : "memory");
-          yy[1] = yy[0];
-#else
-          rd(yy[0], 0);
-#endif
 #pragma unroll
           for (int g = 0; g < DPX; ++g) {
-#if !(TT_MIPS_EXP & 2)
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(yy[g & 1]) : : "memory");
             if (g + 1 < DPX) rd(yy[(g + 1) & 1], g + 1);
-#endif
 #pragma unroll
             for (int n = 0; n < NQ; ++n)
               acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, yy[g & 1]), __builtin_bit_cast(bf16x8, qf[n].v[g]), acc[n], 0, 0, 0);
@@ -640,12 +611,6 @@ __global__ __launch_bounds__(256, 2) void mips_pass1_dma_kernel(const MipsArgs p
         }
       }
       const int off0 = 16 * (2 * PAR + jt);  // group-relative row of element 0 (compile-time: jt is unrolled)
-#if TT_MIPS_EXP & 1
-      // measurement variant (tools/mips_variants.sh): no epilogue -- one add per accumulator quad keeps the MFMAs alive
-#pragma unroll
-      for (int n = 0; n < NQ; ++n) m1[n] += acc[n][0];
-      continue;
-#endif
       auto rows_inside = [&]() {  // elements of this lane's 16 rows inside the corpus (last chunk only)
         // the 64-bit part is wave-uniform (scalar registers); per lane only a 32-bit subtract and clamp
         const int64_t rows_left = p.C - chunk * (CHUNK << g7);
@@ -752,29 +717,13 @@ __global__ __launch_bounds__(256, 2) void mips_pass1_dma_kernel(const MipsArgs p
     // tile t+1 must have landed; tiles t+2 .. t+STAGES-1 may still be in flight
     // NOTE (round 3, ISA): __syncthreads() below is `s_waitcnt vmcnt(0); s_barrier` -- the release fence it carries
     // drains every DMA in flight, so the counted wait in front of it is moot and the 4-stage ring prefetches like a
-    // 2-stage one.  Measured with the variants of tools/mips_variants.sh on one box, bf16 pass 1: product 2.43-2.44 ms,
-    // counted wait + bare s_barrier (64) 2.38-2.42, one tile fewer in flight (192) 2.41-2.44, vmcnt(0) + bare barrier
-    // (320) 2.39 -- all the same: with two workgroups per CU the other workgroup's MFMAs cover the drain, the kernel is
+    // 2-stage one.  Measured with compile-time variants on one box (profiles/HISTORY.md, round 3), bf16 pass 1: product
+    // 2.43-2.44 ms, counted wait + bare s_barrier 2.38-2.42, one tile fewer in flight 2.41-2.44, vmcnt(0) + bare barrier
+    // 2.39 -- all the same: with two workgroups per CU the other workgroup's MFMAs cover the drain, the kernel is
     // not waiting for its corpus stream at this point.  Left as it is.
-#if TT_MIPS_EXP & 128
-    if (more) wait_vmcnt<(STAGES >= 3 ? STAGES - 3 : 0) * NI>();
-    else wait_vmcnt<0>();
-#elif TT_MIPS_EXP & 256
-    wait_vmcnt<0>();
-#else
     if (more) wait_vmcnt<(STAGES - 2) * NI>();
     else wait_vmcnt<0>();
-#endif
-#if TT_MIPS_EXP & 64
-    if constexpr (SHARE) {
-      __syncthreads();
-    } else {
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    }
-#elif !(TT_MIPS_EXP & 4)
     __syncthreads();
-#endif
   };
   using P0 = std::integral_constant<int, 0>;
   using P1 = std::integral_constant<int, 1>;
@@ -1626,11 +1575,7 @@ extern "C" int tt_mips_topk(const void* query, const void* corpus, int dtype, in
         rc = mips_wide_pass(1, a, dtype, wide_ws, wide_bytes, pl.qb, st);
       } else {
         rc = (vec && D == dp && !no_dma) ? dispatch_pass1_dma(dtype, pl.dpx, a, pl.splits, st) : -1;
-#ifdef TT_MIPS_ROWARG
-        a.arg_quads = 0;
-#else
         a.arg_quads = dtype == TT_BF16;  // what the DMA pass left in the gm2 words
-#endif
         a.raw_scores = 1;
         if (rc == -1) {  // generic pass 1 keeps the group maxima only, as score_ord values
           a.gm2 = nullptr;
