@@ -720,6 +720,42 @@ int tt_gather_rows_bf16(const uint16_t* table, int64_t n_rows, int64_t dim, cons
                         int64_t n_ids, float* out, int64_t ld_out, int32_t* oob_flag,
                         tt_stream_t stream);
 
+/* ---------------------------------------------------------------- light ranker (TwoTowerPlusLightRanker)
+ * Per row / candidate: s_n = <R_n, v> (n < NU), p = softmax(s), t = sum_n p_n R_n, m = <u, v>,
+ * z = [v | t | s | m] (Z = 2 DI + NU + 1), logits = W z + b with W [T, Z], b [T].  R is [B, NU, DI] with row stride
+ * ldR (>= NU*DI); R, u, v (and dR, du, dv) 16-byte aligned with row strides that are multiples of 4.
+ * Sizes: 1 <= NU <= 32, 1 <= T <= 16, DI % 4 == 0 and 4 <= DI <= 256 (tt_light_ranker_supported); anything else, a null
+ * pointer, a misaligned operand or (rerank) K outside [1, NI] or NI outside [1, 4096] returns TT_E_BADARG before any
+ * work is enqueued.
+ *
+ * Training head, replaces ref:src/two_tower_plus_light_ranker.py:299-339 (the light ranker's BCE on the impressed
+ * item, torch.cat read along the last axis): loss = mean over B*T of BCE_with_logits(logits, labels).  The forward
+ * keeps z and the logits in `ws` (tt_light_ranker_head_workspace_bytes); the backward reads them with `grad_loss` (device
+ * scalar) and WRITES dR, du (= dm v, the m term only), dv (the head's part), dW and db.  Every reduction runs in a fixed
+ * order, without float atomics: two runs give the same bits. */
+int tt_light_ranker_supported(int64_t NU, int64_t DI, int64_t T);
+int64_t tt_light_ranker_head_workspace_bytes(int64_t B, int64_t NU, int64_t DI, int64_t T);
+int tt_light_ranker_head_fwd(const float* R, int64_t ldR, const float* u, int64_t ldu, const float* v, int64_t ldv,
+                             const float* labels /*[B, T]*/, int64_t B, int64_t NU, int64_t DI, int64_t T,
+                             const float* W, const float* bias, float* loss_out, void* ws, int64_t ws_bytes,
+                             tt_stream_t stream);
+int tt_light_ranker_head_bwd(const float* grad_loss, const float* R, int64_t ldR, const float* u, int64_t ldu,
+                             const float* v, int64_t ldv, const float* labels, int64_t B, int64_t NU, int64_t DI,
+                             int64_t T, const float* W, void* ws, int64_t ws_bytes, float* dR, int64_t lddR, float* du,
+                             int64_t lddu, float* dv, int64_t lddv, float* dW, float* db, tt_stream_t stream);
+/* Rerank, replaces ref:src/two_tower_plus_light_ranker.py:160-207 (gather, bmm, softmax, bmm, cat, Linear, the value
+ * weights, topk, gather): per query b, val_j = (W z_j + b) . uvw for each of its NI candidates (z_j from candidate row j,
+ * score_j = scores[b, j]), then out_ids[b, 0:K] = idx[b, j] of the K largest val_j, ordered by (val desc, j asc).
+ * Candidate rows come from `corpus` [C, DI] by idx (dtype TT_F32, or TT_BF16 widened exactly; ids outside [0, C) score
+ * a zero row and set *oob_flag) OR, with corpus = NULL, from `rows` [B, NI, DI] fp32 (a caller's own MIPS module): exactly
+ * one of the two.  [B, NI, DI] is never formed from the corpus.  out_vals [B, NI] (may be NULL) receives every val_j.
+ * Needs no workspace. */
+int tt_light_ranker_rerank(const void* corpus, int dtype, int64_t C, const int64_t* idx /*[B, NI]*/,
+                           const float* rows, const float* scores /*[B, NI]*/, int64_t B, int64_t NI, int64_t K,
+                           const float* R, int64_t ldR, int64_t NU, int64_t DI, const float* W, const float* bias,
+                           const float* uvw, int64_t T, int64_t* out_ids /*[B, K]*/, float* out_vals,
+                           int32_t* oob_flag, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ import sys
 
 _MODULES = ("baseline_mips_module", "two_tower_base_retrieval", "two_tower_with_user_history_encoder",
             "two_tower_with_debiasing", "two_tower_with_position_debiased_weights", "two_tower_with_user_debiased_weights",
-            "user_history_encoder")
+            "user_history_encoder", "two_tower_plus_light_ranker")
 for _name in _MODULES:
     _mod = importlib.import_module(f"two_tower_models_amd.{_name}")
     sys.modules[f"{__name__}.{_name}"] = _mod

@@ -1686,3 +1686,108 @@ def gather_corpus_rows(corpus: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     else:
         gather_rows_into(corpus, flat, out)
     return out.view(B, K, D)
+
+
+# ----------------------------------------------------------------- light ranker (TwoTowerPlusLightRanker)
+def light_ranker_supported(NU: int, DI: int, T: int) -> bool:
+    """Sizes the fused light-ranker kernels take (tt_light_ranker_supported): NU <= 32, T <= 16, DI % 4 == 0, DI <= 256."""
+    return bool(N.load().tt_light_ranker_supported(NU, DI, T))
+
+
+def _lr_operand(t: torch.Tensor) -> torch.Tensor:
+    """fp32 row-major with a 16-byte aligned base and a row stride that is a multiple of 4 (the kernels' float4 rows)."""
+    t = _rowmajor(t)
+    if t.data_ptr() % 16 or t.stride(0) % 4:
+        t = t.contiguous()
+        if t.data_ptr() % 16:
+            t = t.clone()
+    return t
+
+
+class LightRankerHead(torch.autograd.Function):
+    """mean over B*T of BCE_with_logits(W [v | t | s | m] + b, labels) with s_n = <R_n, v>, p = softmax(s),
+    t = p^T R, m = <u, v> (ref:src/two_tower_plus_light_ranker.py:299-339, upstream's torch.cat(dim=2) read as the last
+    axis).  R [B, NU, DI] (or [B, NU*DI]), u, v [B, DI], labels [B, T] float32, W [T, 2 DI + NU + 1], b [T].  Two
+    launches per direction (tt_light_ranker_head_fwd / _bwd), fixed-order reductions: bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, R, u, v, labels, W, b):
+        dev = N.require_device(R, u, v, labels, W, b)
+        lib = N.load()
+        if any(t.dtype != torch.float32 for t in (R, u, v, labels, W, b)):
+            raise TypeError("LightRankerHead: float32 operands expected")
+        B, DI = u.shape
+        T = labels.shape[1]
+        NU = R.numel() // (B * DI)
+        if R.shape[0] != B or R.numel() != B * NU * DI or W.shape != (T, 2 * DI + NU + 1) or v.shape != u.shape:
+            raise ValueError("LightRankerHead: R [B, NU, DI], u, v [B, DI], labels [B, T], W [T, 2 DI + NU + 1]")
+        R2 = _lr_operand(R.reshape(B, NU * DI))
+        u, v = _lr_operand(u), _lr_operand(v)
+        labels, W, b = labels.contiguous(), W.contiguous(), b.contiguous()
+        wsn = lib.tt_light_ranker_head_workspace_bytes(B, NU, DI, T)
+        ws = torch.empty(wsn, dtype=torch.uint8, device=dev)  # z, logits: kept for the backward
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        N.check(lib.tt_light_ranker_head_fwd(R2.data_ptr(), R2.stride(0), u.data_ptr(), u.stride(0), v.data_ptr(), v.stride(0),
+                                             labels.data_ptr(), B, NU, DI, T, W.data_ptr(), b.data_ptr(), loss.data_ptr(),
+                                             ws.data_ptr(), wsn, N.stream()), "tt_light_ranker_head_fwd")
+        ctx.shape = (B, NU, DI, T, tuple(R.shape))
+        ctx.save_for_backward(R2, u, v, labels, W, ws)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        R2, u, v, labels, W, ws = ctx.saved_tensors
+        B, NU, DI, T, r_shape = ctx.shape
+        dev = R2.device
+        g = g.contiguous().to(torch.float32)
+        dR = torch.empty(B, NU * DI, dtype=torch.float32, device=dev)
+        du = torch.empty(B, DI, dtype=torch.float32, device=dev)
+        dv = torch.empty(B, DI, dtype=torch.float32, device=dev)
+        dW = torch.empty_like(W)
+        db = torch.empty(T, dtype=torch.float32, device=dev)
+        N.check(N.load().tt_light_ranker_head_bwd(g.data_ptr(), R2.data_ptr(), R2.stride(0), u.data_ptr(), u.stride(0),
+                                                  v.data_ptr(), v.stride(0), labels.data_ptr(), B, NU, DI, T, W.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), dR.data_ptr(), NU * DI, du.data_ptr(), DI,
+                                                  dv.data_ptr(), DI, dW.data_ptr(), db.data_ptr(), N.stream()),
+                "tt_light_ranker_head_bwd")
+        return dR.view(r_shape), du, dv, None, dW, db
+
+
+def light_ranker_rerank(R: torch.Tensor, W: torch.Tensor, b: torch.Tensor, uvw: torch.Tensor, idx: torch.Tensor,
+                        scores: torch.Tensor, k: int, corpus: Optional[torch.Tensor] = None,
+                        rows: Optional[torch.Tensor] = None, return_values: bool = False):
+    """Top k of the [B, NI] MIPS candidates by (W [row | t | s | score] + b) . uvw, ties to the lower candidate
+    position (ref:src/two_tower_plus_light_ranker.py:160-207) -> item ids [B, k] int64 (and, with return_values, every
+    value [B, NI]).  Candidate rows: `corpus` [C, DI] (fp32 or bf16) read by `idx`, or `rows` [B, NI, DI] fp32 (a
+    caller's own MIPS module's third output): exactly one.  One launch (tt_light_ranker_rerank)."""
+    dev = N.require_device(R, W, b, uvw, idx, scores, corpus, rows)
+    lib = N.load()
+    B, NI = idx.shape
+    T, DI = W.shape[0], R.shape[-1]
+    NU = R.numel() // (B * DI)
+    if not (0 < k <= NI):
+        raise RuntimeError("selected index k out of range")  # torch.topk's message
+    if W.shape != (T, 2 * DI + NU + 1) or scores.shape != (B, NI) or idx.dtype != torch.int64:
+        raise ValueError("light_ranker_rerank: R [B, NU, DI], W [T, 2 DI + NU + 1], idx int64 [B, NI], scores [B, NI]")
+    if (corpus is None) == (rows is None):
+        raise ValueError("light_ranker_rerank: pass exactly one of corpus / rows")
+    R2 = _lr_operand(R.reshape(B, NU * DI).to(torch.float32))
+    W, b, uvw = W.contiguous(), b.contiguous(), uvw.to(torch.float32).contiguous()
+    idx, scores = idx.contiguous(), scores.to(torch.float32).contiguous()
+    dtype, C = N.TT_F32, 0
+    if corpus is not None:
+        if corpus.dtype not in (torch.float32, torch.bfloat16) or corpus.dim() != 2 or corpus.shape[1] != DI:
+            raise TypeError("corpus must be float32 or bfloat16 [C, DI]")
+        corpus = corpus.contiguous()
+        dtype, C = (N.TT_BF16 if corpus.dtype == torch.bfloat16 else N.TT_F32), corpus.shape[0]
+    else:
+        rows = rows.to(torch.float32).contiguous()
+        if rows.shape != (B, NI, DI):
+            raise ValueError("rows must be [B, NI, DI]")
+    out = torch.empty(B, k, dtype=torch.int64, device=dev)
+    vals = torch.empty(B, NI, dtype=torch.float32, device=dev) if return_values else None
+    N.check(lib.tt_light_ranker_rerank(N.ptr(corpus), dtype, C, idx.data_ptr(), N.ptr(rows), scores.data_ptr(), B, NI, k,
+                                       R2.data_ptr(), R2.stride(0), NU, DI, W.data_ptr(), b.data_ptr(), uvw.data_ptr(), T,
+                                       out.data_ptr(), N.ptr(vals), N.oob.flag(dev).data_ptr(), N.stream()),
+            "tt_light_ranker_rerank")
+    return (out, vals) if return_values else out
