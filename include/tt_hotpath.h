@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define TT_ABI_VERSION 4
+#define TT_ABI_VERSION 5
 
 #define TT_E_BADARG (-1)      /* null pointer / negative size / unsupported shape */
 #define TT_E_WORKSPACE (-2)   /* ws_bytes smaller than tt_*_workspace_bytes()     */
@@ -105,73 +105,55 @@ int tt_colsum_f32(const float* X, int64_t M, int64_t N, int64_t ldx, float* out,
                   int64_t ws_bytes, tt_stream_t stream);
 
 /* ---------------------------------------------------------------- K3 fused tower
- * One tower of TwoTowerBaseRetrieval in ONE launch per direction:
- *   y = Linear(2D -> D)([ table[id] | Linear(hidden -> D)(ReLU(Linear(F -> hidden)(features))) ])
+ * A tower of TwoTowerBaseRetrieval in ONE launch per direction:
+ *   y = Linear(2D + E -> D)([ table[id] | Linear(hidden -> D)(ReLU(Linear(F -> hidden)(features))) | extra[B, E] ])
  * replaces nn.Embedding + nn.Sequential + torch.cat + nn.Linear at ref:src/two_tower_base_retrieval.py:129-162,164-191
  * (user tower) and :193-219 (item tower).  The forward also writes what the backward needs: h_out [B, hidden] (the ReLU
- * output) and tin_out [B, 2D] (the tower input).  tt_tower_bwd_data is the data side of their autograd:
- *   d_tin = dy W3;  d_emb = d_tin[:, :D] (embedding-row gradients);  d_f = d_tin[:, D:];  dh = (d_f W2) (.) [h > 0]
- * and tt_tower_bwd_weights the parameter side -- dW3 = dy^T tin, dW2 = d_f^T h, dW1 = dh^T features and the three
- * bias sums (autograd of the nn.Linear layers of the same lines) -- in one product launch over 64-row blocks plus one
- * deterministic reduce over the blocks' partials (`ws`: tt_tower_bwd_weights_workspace_bytes) instead of three
- * tt_gemm_tn_colsum_f32 calls.
- * Shapes: hidden = 256, D = d_out in {32, 64, 128}, F <= 64, 16-B aligned rows (tt_tower_supported says);
+ * output) and tin_out [B, 2D] (the tower input; the extra block is the caller's own tensor).  tt_tower_bwd_data is the
+ * data side of their autograd:
+ *   d_tin = dy W3;  d_emb = d_tin[:, :D] (embedding-row gradients);  d_f = d_tin[:, D:2D];  d_extra = d_tin[:, 2D:];
+ *   dh = (d_f W2) (.) [h > 0]
+ * and tt_tower_bwd_weights the parameter side -- dW3 = dy^T [tin | extra], dW2 = d_f^T h, dW1 = dh^T features and the
+ * three bias sums (autograd of the nn.Linear layers of the same lines) -- in one product launch over 64-row blocks plus
+ * one deterministic reduce over the blocks' partials (`ws`: tt_tower_bwd_weights_workspace_bytes, one per side) instead
+ * of three tt_gemm_tn_colsum_f32 calls.
+ * The third, dense input block (E = 2D; E = 0: none, `extra` / `d_extra` unused) is TwoTowerWithUserHistoryEncoder's
+ * user tower, whose input gains the history encoder's [recent | mean] summary
+ * (ref:src/two_tower_with_user_history_encoder.py:81-83 the Linear(2*DU + 2*DI -> DI), :85-122 the cat): W3 / dW3 are
+ * [D, 2D + E] row-major, d_extra [B, E] is the gradient that flows back into the encoder.
+ * Each call takes n_sides = 1 or 2 tower descriptors (a host array; B, D, hidden and E are the same for both).  Two sides
+ * are BOTH towers of TwoTowerBaseRetrieval per launch (user tower = sides[0], item tower = sides[1]; blockIdx.y picks the
+ * tower, the arithmetic is the one-tower kernels' own, so the results are the same bits): for steps that run on ONE
+ * stream -- a whole-step hipGraph, batches too small for the two-stream fork -- where two launches of a 128-workgroup
+ * kernel ran back to back on a 256-CU chip (ref:src/two_tower_base_retrieval.py:129-219, both towers' forward, and their
+ * autograd).  Two sides take no third block (E != 0: TT_E_UNSUPPORTED); any other n_sides is TT_E_BADARG.
+ * Shapes: hidden = 256, D = d_out in {32, 64, 128}, F <= 64, E in {0, 2D}, 16-B aligned rows (tt_tower_supported says);
  * anything else returns TT_E_UNSUPPORTED -- use tt_gather_rows + tt_gemm_f32. */
-int tt_tower_supported(int64_t D, int64_t F, int64_t hidden, int64_t d_out);
-int tt_tower_fwd(const float* table, int64_t n_rows, const int64_t* ids, const float* feats, int64_t ldf, int64_t B,
-                 int64_t D, int64_t F, int64_t hidden, const float* W1, const float* b1, const float* W2, const float* b2,
-                 const float* W3, const float* b3, int64_t d_out, float* y, int64_t ldy, float* h_out, float* tin_out,
-                 int32_t* oob_flag, tt_stream_t stream);
-int tt_tower_bwd_data(const float* dy, int64_t ldy, int64_t B, int64_t D, int64_t hidden, const float* W2, const float* W3,
-                      const float* h, float* d_emb, int64_t ld_demb, float* d_f, float* dh, tt_stream_t stream);
-int64_t tt_tower_bwd_weights_workspace_bytes(int64_t B, int64_t D, int64_t F, int64_t hidden);
-int tt_tower_bwd_weights(const float* dy, int64_t ldy, const float* tin, const float* d_f, const float* h, const float* dh,
-                         const float* feats, int64_t ldf, int64_t B, int64_t D, int64_t F, int64_t hidden, float* dW1,
-                         float* db1, float* dW2, float* db2, float* dW3, float* db3, void* ws, int64_t ws_bytes,
-                         tt_stream_t stream);
-/* The same three entry points for a tower whose input has a THIRD, dense block:
- *   y = Linear(2D + E -> D)([ table[id] | feature MLP | extra[B, E] ]),  E = 2D  (E = 0: the functions above)
- * = TwoTowerWithUserHistoryEncoder's user tower, whose input gains the history encoder's [recent | mean] summary
- * (ref:src/two_tower_with_user_history_encoder.py:81-83 the Linear(2*DU + 2*DI -> DI), :85-122 the cat).  W3 / dW3 are
- * [D, 2D + E] row-major, tin_out stays [B, 2D] (the extra block is the caller's own tensor), d_extra [B, E] is the
- * gradient that flows back into the encoder. */
-/* BOTH towers of TwoTowerBaseRetrieval per launch (user tower = sides[0], item tower = sides[1]; blockIdx.y picks the tower,
- * the arithmetic is tt_tower_fwd / _bwd_data / _bwd_weights' own, so the results are the same bits): for steps that run on
- * ONE stream -- a whole-step hipGraph, batches too small for the two-stream fork -- where two launches of a 128-workgroup
- * kernel ran back to back on a 256-CU chip.  Same shape limits, D the same for both towers, no third input block.
- * ref:src/two_tower_base_retrieval.py:129-219 (both towers' forward), their autograd. */
 typedef struct {
   const float* table; int64_t n_rows; const int64_t* ids; const float* feats; int64_t ldf; int64_t F;
   const float *W1, *b1, *W2, *b2, *W3, *b3;
   float* y; int64_t ldy; float* h_out; float* tin_out;
+  const float* extra; int64_t ldx;
 } tt_tower_fwd_side;
 typedef struct {
   const float* dy; int64_t ldy; const float *W2, *W3, *h;
   float* d_emb; int64_t ld_demb; float* d_f; float* dh;
+  float* d_extra; int64_t ld_dx;
 } tt_tower_bwd_side;
 typedef struct {
   const float* dy; int64_t ldy; const float *tin, *d_f, *h, *dh, *feats; int64_t ldf; int64_t F;
   float *dW1, *db1, *dW2, *db2, *dW3, *db3;
-  void* ws; int64_t ws_bytes; /* tt_tower_bwd_weights_workspace_bytes(B, D, F, hidden), one per side */
+  void* ws; int64_t ws_bytes; /* tt_tower_bwd_weights_workspace_bytes(B, D, F, hidden, E) */
+  const float* extra; int64_t ldx;
 } tt_tower_wgrad_side;
-int tt_tower_fwd_pair(const tt_tower_fwd_side* sides /*host, 2*/, int64_t B, int64_t D, int64_t hidden, int32_t* oob_flag,
-                      tt_stream_t stream);
-int tt_tower_bwd_data_pair(const tt_tower_bwd_side* sides /*host, 2*/, int64_t B, int64_t D, int64_t hidden, tt_stream_t stream);
-int tt_tower_bwd_weights_pair(const tt_tower_wgrad_side* sides /*host, 2*/, int64_t B, int64_t D, int64_t hidden,
-                              tt_stream_t stream);
-int tt_tower_x_supported(int64_t D, int64_t F, int64_t hidden, int64_t d_out, int64_t E);
-int tt_tower_fwd_x(const float* table, int64_t n_rows, const int64_t* ids, const float* feats, int64_t ldf, int64_t B,
-                   int64_t D, int64_t F, int64_t hidden, const float* W1, const float* b1, const float* W2, const float* b2,
-                   const float* W3, const float* b3, int64_t d_out, const float* extra, int64_t ldx, int64_t E, float* y,
-                   int64_t ldy, float* h_out, float* tin_out, int32_t* oob_flag, tt_stream_t stream);
-int tt_tower_bwd_data_x(const float* dy, int64_t ldy, int64_t B, int64_t D, int64_t hidden, const float* W2, const float* W3,
-                        const float* h, float* d_emb, int64_t ld_demb, float* d_f, float* dh, float* d_extra, int64_t ld_dx,
-                        int64_t E, tt_stream_t stream);
-int64_t tt_tower_bwd_weights_x_workspace_bytes(int64_t B, int64_t D, int64_t F, int64_t hidden, int64_t E);
-int tt_tower_bwd_weights_x(const float* dy, int64_t ldy, const float* tin, const float* d_f, const float* h, const float* dh,
-                           const float* feats, int64_t ldf, const float* extra, int64_t ldx, int64_t E, int64_t B, int64_t D,
-                           int64_t F, int64_t hidden, float* dW1, float* db1, float* dW2, float* db2, float* dW3, float* db3,
-                           void* ws, int64_t ws_bytes, tt_stream_t stream);
+int tt_tower_supported(int64_t D, int64_t F, int64_t hidden, int64_t d_out, int64_t E);
+int tt_tower_fwd(const tt_tower_fwd_side* sides /*host*/, int32_t n_sides, int64_t B, int64_t D, int64_t hidden, int64_t E,
+                 int32_t* oob_flag, tt_stream_t stream);
+int tt_tower_bwd_data(const tt_tower_bwd_side* sides /*host*/, int32_t n_sides, int64_t B, int64_t D, int64_t hidden,
+                      int64_t E, tt_stream_t stream);
+int64_t tt_tower_bwd_weights_workspace_bytes(int64_t B, int64_t D, int64_t F, int64_t hidden, int64_t E);
+int tt_tower_bwd_weights(const tt_tower_wgrad_side* sides /*host*/, int32_t n_sides, int64_t B, int64_t D, int64_t hidden,
+                         int64_t E, tt_stream_t stream);
 
 /* ---------------------------------------------------------------- K5 in-batch softmax CE
  * Forward: S = U I^T is never written to memory.

@@ -35,6 +35,17 @@ def test_argument_validation_needs_no_gpu():
     assert lib.tt_gemm_workspace_bytes(N.TT_GEMM_TN, 128, 384, 409600) > 0
     assert lib.tt_inbatch_ce_workspace_bytes(8192, 8192, 128) > 0
     assert lib.tt_inbatch_ce_workspace_bytes(8192, 8192, 256) >= 8192 * 8192 * 4  # D > 128: logits materialised
+    # the fused tower: D, F, hidden, d_out, third-block width E
+    assert [lib.tt_tower_supported(*a) for a in ((128, 8, 256, 128, 0), (128, 8, 256, 128, 256), (128, 8, 256, 128, 64),
+                                                 (96, 8, 256, 96, 0))] == [1, 1, 0, 0]
+    # one or two sides per call, two without a third block; refused before any HIP call (B = 64, D = 128, hidden = 256)
+    for call, side in ((lambda s, n, E: lib.tt_tower_fwd(s, n, 64, 128, 256, E, None, None), N.TowerFwdSide),
+                       (lambda s, n, E: lib.tt_tower_bwd_data(s, n, 64, 128, 256, E, None), N.TowerBwdSide),
+                       (lambda s, n, E: lib.tt_tower_bwd_weights(s, n, 64, 128, 256, E, None), N.TowerWgradSide)):
+        assert call(None, 1, 0) == N.TT_E_BADARG
+        assert call((side * 3)(), 0, 0) == N.TT_E_BADARG and call((side * 3)(), 3, 0) == N.TT_E_BADARG
+        assert call((side * 2)(), 2, 256) == N.TT_E_UNSUPPORTED
+        assert call(side(), 1, 0) == N.TT_E_BADARG and b"null pointer" in lib.tt_last_error_string()
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU refusal")

@@ -899,7 +899,7 @@ def test_gemm_weights_stationary_path(T, layout, M, Nn, K):
 
 @pytest.mark.parametrize("B,D,F", [(8192, 128, 8), (100, 128, 64), (333, 64, 20), (65, 32, 1), (1, 128, 33)])
 def test_tower_weight_gradients_kernel_vs_fp64(T, B, D, F):
-    """tt_tower_bwd_weights (block partials in one launch + one reduce) on its own: dW3 = dy^T tin, dW2 = d_f^T h,
+    """tt_tower_bwd_weights with one side (block partials in one launch + one reduce) on its own: dW3 = dy^T tin, dW2 = d_f^T h,
     dW1 = dh^T x and the three bias sums against float64 products, incl. a ragged last 64-row block, one row, F = 64;
     and bit-identical from call to call (the reduce adds the partials in block order)."""
     ops, N = T
@@ -919,7 +919,7 @@ def test_tower_weight_gradients_kernel_vs_fp64(T, B, D, F):
 @pytest.mark.parametrize("B,D,F,n_rows", [(4096, 128, 8, 100_000), (100, 128, 8, 50), (333, 64, 20, 1000), (65, 32, 8, 200),
                                           (1, 128, 33, 7), (8192, 128, 8, 5000)])  # > 4096 rows: the 64-row-per-workgroup form
 def test_fused_tower_with_third_input_block_forward_and_backward(T, B, D, F, n_rows):
-    """tt_tower_fwd_x / tt_tower_bwd_data_x / tt_tower_bwd_weights_x: the history model's user tower
+    """tt_tower_fwd / _bwd_data / _bwd_weights with the third input block (E = 2D): the history model's user tower
     [ id | MLP | recent | mean ] -> Linear(4D -> D) (ref:src/two_tower_with_user_history_encoder.py:81-83,85-122) as one
     kernel per direction, against the same lines in float64 torch on the CPU: output, all six parameter gradients, the
     embedding-row gradients and the gradient that flows back into the encoder summary; ragged last block, one row,
@@ -962,7 +962,7 @@ def test_fused_tower_with_third_input_block_forward_and_backward(T, B, D, F, n_r
 @pytest.mark.parametrize("B,D,F,n_rows", [(8192, 128, 8, 100_000), (100, 128, 8, 50), (333, 64, 20, 1000), (64, 32, 8, 200),
                                           (1, 128, 33, 7), (4200, 64, 8, 5000)])  # > 4096 rows: the 64-row-per-workgroup form
 def test_fused_tower_matches_oracle_forward_and_backward(T, B, D, F, n_rows):
-    """tt_tower_fwd / tt_tower_bwd_data (one launch per direction: lookup + feature MLP + cat + tower Linear,
+    """tt_tower_fwd / tt_tower_bwd_data with one side (one launch per direction: lookup + feature MLP + cat + tower Linear,
     ref:src/two_tower_base_retrieval.py:129-219) against the CPU oracle's item tower: output, every parameter gradient,
     and the embedding-row gradients (dense form), incl. duplicate ids and a ragged last 64-row block."""
     ops, N = T
@@ -994,7 +994,7 @@ def test_fused_tower_matches_oracle_forward_and_backward(T, B, D, F, n_rows):
 
 @pytest.mark.parametrize("B,D,Fu,Fi", [(300, 64, 5, 20), (8192, 128, 8, 8), (4096, 32, 16, 3), (33, 128, 8, 8)])
 def test_tower_pair_launches_are_the_single_tower_kernels_bit_for_bit(B, D, Fu, Fi):
-    """tt_tower_*_pair (both towers of the base model per launch: ops.FusedTowerPair) against two ops.FusedTower calls:
+    """tt_tower_* with two sides (both towers of the base model per launch: ops.FusedTowerPair) against two ops.FusedTower calls:
     embeddings and every gradient -- table rows, the six weight / bias tensors of each tower -- identical bits."""
     import torch.nn as nn
     from two_tower_models_amd import ops

@@ -677,7 +677,7 @@ def test_exchanges_are_issued_before_and_waited_after_the_kernels_meant_to_cover
         tr, N.trace = N.trace, None
         torch.cuda.synchronize()
         where = lambda name: [i for i, n in enumerate(tr) if n == name]
-        fwd, bwd = where("tt_tower_fwd_x"), where("tt_tower_bwd_data_x")
+        fwd, bwd = where("tt_tower_fwd"), where("tt_tower_bwd_data")
         assert len(fwd) == 2 and len(bwd) == 2, tr  # forward: item tower, user tower; backward: user tower, item tower
         rows_issued = where("issue:lookup_rows_alltoall")
         assert len(rows_issued) == 2 and max(rows_issued) < fwd[0], tr

@@ -20,7 +20,7 @@ cfg = dict(bench.WORKLOADS[wl])
 batches = bench.make_batches(cfg, 16, dev)
 POINTS = [("parked rows, the library's release point", None, 0), ("tt_hist_embed_pool", "tt_hist_embed_pool", 1), ("in-proj 0", "tt_gemm_f32", 5), ("attn fwd 0", "tt_attn_fwd", 1),
           ("in-proj 1", "tt_gemm_f32", 6), ("attn fwd 1", "tt_attn_fwd", 2), ("enc_last fwd", "tt_enc_last_fwd", 1),
-          ("user tower fwd", "tt_tower_fwd_x", 1), ("ce fwd", "tt_inbatch_ce_fwd_du_loss", 1), ("ce bwd", "tt_inbatch_ce_bwd", 1),
+          ("user tower fwd", "tt_tower_fwd", 1), ("ce fwd", "tt_inbatch_ce_fwd_du_loss", 1), ("ce bwd", "tt_inbatch_ce_bwd", 1),
           ("enc_last bwd", "tt_enc_last_bwd_data", 1), ("attn bwd 1", "tt_attn_bwd", 1), ("attn bwd 0", "tt_attn_bwd", 2)]
 real_check = N.check
 state = {"opt": None, "name": None, "occ": 0, "seen": 0, "busy": False, "in_step": False}

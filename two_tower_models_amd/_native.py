@@ -23,7 +23,7 @@ TT_COMM_ID_BYTES = 128
 TT_COMM_F32, TT_COMM_I32, TT_COMM_I64, TT_COMM_U8 = 0, 1, 2, 3
 TT_COMM_SUM, TT_COMM_MAX = 0, 1
 TT_MAX_GRAD_SOURCES = 4
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _vp, _i64, _i32, _int = C.c_void_p, C.c_int64, C.c_int32, C.c_int
 
@@ -64,14 +64,15 @@ class TowerFwdSide(C.Structure):
     """tt_tower_fwd_side."""
 
     _fields_ = [("table", _vp), ("n_rows", _i64), ("ids", _vp), ("feats", _vp), ("ldf", _i64), ("F", _i64), ("W1", _vp), ("b1", _vp),
-                ("W2", _vp), ("b2", _vp), ("W3", _vp), ("b3", _vp), ("y", _vp), ("ldy", _i64), ("h_out", _vp), ("tin_out", _vp)]
+                ("W2", _vp), ("b2", _vp), ("W3", _vp), ("b3", _vp), ("y", _vp), ("ldy", _i64), ("h_out", _vp), ("tin_out", _vp),
+                ("extra", _vp), ("ldx", _i64)]
 
 
 class TowerBwdSide(C.Structure):
     """tt_tower_bwd_side."""
 
     _fields_ = [("dy", _vp), ("ldy", _i64), ("W2", _vp), ("W3", _vp), ("h", _vp), ("d_emb", _vp), ("ld_demb", _i64), ("d_f", _vp),
-                ("dh", _vp)]
+                ("dh", _vp), ("d_extra", _vp), ("ld_dx", _i64)]
 
 
 class TowerWgradSide(C.Structure):
@@ -79,7 +80,7 @@ class TowerWgradSide(C.Structure):
 
     _fields_ = [("dy", _vp), ("ldy", _i64), ("tin", _vp), ("d_f", _vp), ("h", _vp), ("dh", _vp), ("feats", _vp), ("ldf", _i64),
                 ("F", _i64), ("dW1", _vp), ("db1", _vp), ("dW2", _vp), ("db2", _vp), ("dW3", _vp), ("db3", _vp), ("ws", _vp),
-                ("ws_bytes", _i64)]
+                ("ws_bytes", _i64), ("extra", _vp), ("ldx", _i64)]
 
 
 class PlanJob(C.Structure):
@@ -121,26 +122,17 @@ SIGNATURES = {
     "tt_gemm_tn_colsum_f32": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _i64, _vp]),
     "tt_colsum_workspace_bytes": (_i64, [_i64, _i64]),
     "tt_colsum_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
-    "tt_tower_supported": (_int, [_i64, _i64, _i64, _i64]),
-    "tt_tower_fwd": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
-                            _vp, _vp, _vp, _vp]),
-    "tt_tower_bwd_data": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "tt_tower_bwd_weights_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
-    "tt_tower_bwd_weights": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, _vp, _i64, _vp]),
+    "tt_tower_supported": (_int, [_i64, _i64, _i64, _i64, _i64]),
+    "tt_tower_fwd": (_int, [C.POINTER(TowerFwdSide), _i32, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "tt_tower_bwd_data": (_int, [C.POINTER(TowerBwdSide), _i32, _i64, _i64, _i64, _i64, _vp]),
+    "tt_tower_bwd_weights_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
+    "tt_tower_bwd_weights": (_int, [C.POINTER(TowerWgradSide), _i32, _i64, _i64, _i64, _i64, _vp]),
     "tt_adam_begin_ids": (_int, [_vp, _vp, _i64, C.POINTER(AdamStashJob), _i32, _vp]),
     "tt_adam_begin_ids_planes": (_int, [_vp, _vp, _i64, C.POINTER(AdamStashJob), _i32, _i32, _vp]),
     "tt_adam_tables_finish": (_int, [C.POINTER(AdamFinishJob), _i32, _vp, _vp]),
     "tt_inbatch_ce_fwd_du_loss": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                          _vp, _vp, _i64, _vp]),
     "tt_scale_rows_g": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
-    "tt_tower_x_supported": (_int, [_i64, _i64, _i64, _i64, _i64]),
-    "tt_tower_fwd_x": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                              _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "tt_tower_bwd_data_x": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp]),
-    "tt_tower_bwd_weights_x_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
-    "tt_tower_bwd_weights_x": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
-                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "tt_inbatch_ce_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "tt_inbatch_ce_fwd": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "tt_inbatch_ce_bwd": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp,
@@ -206,9 +198,6 @@ SIGNATURES = {
     "tt_stream_copy": (_int, [_vp, _vp, _i64, _vp]),
     "tt_mfma_probe_flops": (_i64, [_int, _i32]),
     "tt_mfma_probe": (_int, [_int, _i32, _vp, _i64, _vp]),
-    "tt_tower_fwd_pair": (_int, [C.POINTER(TowerFwdSide), _i64, _i64, _i64, _vp, _vp]),
-    "tt_tower_bwd_data_pair": (_int, [C.POINTER(TowerBwdSide), _i64, _i64, _i64, _vp]),
-    "tt_tower_bwd_weights_pair": (_int, [C.POINTER(TowerWgradSide), _i64, _i64, _i64, _vp]),
     "tt_rowgrad_plan_jobs_supported": (_int, [_i64]),
     "tt_rowgrad_plan_jobs": (_int, [C.POINTER(PlanJob), _i32, _vp, _vp]),
     "tt_route_workspace_bytes": (_i64, [_i64, _i32]),

@@ -17,7 +17,7 @@
 // Shapes: hidden = 256 (fixed upstream), D in {32, 64, 128}, F <= 64, 16-B aligned rows; anything else returns
 // TT_E_UNSUPPORTED and the caller takes the GEMM path.
 //
-// XTRA variants (tt_tower_*_x): the tower input has a third, dense block -- [ id | MLP | extra[B, 2D] ], tower
+// XTRA variants (tt_tower_* with E = 2D): the tower input has a third, dense block -- [ id | MLP | extra[B, 2D] ], tower
 // Linear(4D -> D) -- which is TwoTowerWithUserHistoryEncoder's user tower (extra = the encoder's [recent | mean]
 // summary; ref:src/two_tower_with_user_history_encoder.py:81-83,85-122).  The extra block takes the place of the hidden
 // activations in LDS once they are consumed (same [64][2D + 4] image as the tower input), the last product runs as
@@ -203,7 +203,7 @@ __device__ __forceinline__ void tower_fwd_body(const TowerFwdArgs& p) {
 
 template <int DE8, bool XTRA, int RT>
 __global__ __launch_bounds__(256) void tower_fwd_kernel(const TowerFwdArgs p) { tower_fwd_body<DE8, XTRA, RT>(p); }
-// BOTH towers of the base model in one launch (blockIdx.y = tower; tt_tower_fwd_pair): the same body, so the same bits.  One
+// BOTH towers of the base model in one launch (blockIdx.y = tower; tt_tower_fwd with two sides): the same body, so the same bits.  One
 // tower is at most 128 workgroups -- half the chip -- and a step that runs on ONE stream (a hipGraph capture, batches too
 // small for the two-stream fork) paid for the two launches back to back.
 struct TowerFwdArgs2 { TowerFwdArgs t[2]; };
@@ -499,265 +499,187 @@ static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p)
 
 using namespace tt;
 
-extern "C" int tt_tower_supported(int64_t D, int64_t F, int64_t hidden, int64_t d_out) {
-  return tower_shape_ok(D, F, hidden, d_out) ? 1 : 0;
-}
-extern "C" int tt_tower_x_supported(int64_t D, int64_t F, int64_t hidden, int64_t d_out, int64_t E) {
+extern "C" int tt_tower_supported(int64_t D, int64_t F, int64_t hidden, int64_t d_out, int64_t E) {
   return (tower_shape_ok(D, F, hidden, d_out) && (E == 0 || E == 2 * D)) ? 1 : 0;
-}
-
-extern "C" int tt_tower_fwd_x(const float* table, int64_t n_rows, const int64_t* ids, const float* feats, int64_t ldf,
-                              int64_t B, int64_t D, int64_t F, int64_t hidden, const float* W1, const float* b1,
-                              const float* W2, const float* b2, const float* W3, const float* b3, int64_t d_out,
-                              const float* extra, int64_t ldx, int64_t E, float* y, int64_t ldy, float* h_out,
-                              float* tin_out, int32_t* oob_flag, tt_stream_t stream) {
-  if (!table || !ids || !feats || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !y || !h_out || !tin_out || (E > 0 && !extra))
-    return fail_arg("tt_tower_fwd: null pointer");
-  if (B <= 0 || n_rows <= 0 || ldf < F || ldy < d_out || E < 0 || (E > 0 && ldx < E)) return fail_arg("tt_tower_fwd: sizes");
-  if (!tt_tower_x_supported(D, F, hidden, d_out, E) || ldy % 4 || !al16p(table) || !al16p(W2) || !al16p(W3) || !al16p(y) ||
-      !al16p(h_out) || !al16p(tin_out) || (E > 0 && (ldx % 4 || !al16p(extra)))) {
-    set_error("tt_tower_fwd: needs hidden = 256, D = d_out in {32, 64, 128}, F <= 64, extra width 0 or 2D, 16-B aligned operands");
-    return TT_E_UNSUPPORTED;
-  }
-  TowerFwdArgs a{table, n_rows, ids, feats, ldf, B, F, W1, b1, W2, b2, W3, b3, y, ldy, h_out, tin_out, oob_flag, extra, ldx};
-  hipStream_t st = S(stream);
-  const int rt = tower_row_tiles(B);
-  const int rows = 32 * rt;
-  const unsigned grid = (unsigned)ceil_div(B, rows);
-  const size_t lds = (size_t)(rows * (TW_HID + 4) + rows * (2 * D + 4) + rows * F) * sizeof(float);
-#define TT_TWF1(E8, X, R)                                                                                                \
-  {                                                                                                                      \
-    if (lds > 64 * 1024) {                                                                                               \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_fwd_kernel<E8, X, R>),                     \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-      if (e != hipSuccess) { set_error("tower_fwd_kernel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; } \
-    }                                                                                                                    \
-    tower_fwd_kernel<E8, X, R><<<grid, 256, lds, st>>>(a);                                                               \
-  }
-#define TT_TWF(E8, X) { if (rt == 1) TT_TWF1(E8, X, 1) else TT_TWF1(E8, X, 2) }
-  if (E == 0) {
-    if (D == 32) TT_TWF(4, false) else if (D == 64) TT_TWF(8, false) else TT_TWF(16, false)
-  } else {
-    if (D == 32) TT_TWF(4, true) else if (D == 64) TT_TWF(8, true) else TT_TWF(16, true)
-  }
-#undef TT_TWF
-#undef TT_TWF1
-  return check_launch("tower_fwd_kernel");
-}
-
-extern "C" int tt_tower_fwd(const float* table, int64_t n_rows, const int64_t* ids, const float* feats, int64_t ldf,
-                            int64_t B, int64_t D, int64_t F, int64_t hidden, const float* W1, const float* b1,
-                            const float* W2, const float* b2, const float* W3, const float* b3, int64_t d_out, float* y,
-                            int64_t ldy, float* h_out, float* tin_out, int32_t* oob_flag, tt_stream_t stream) {
-  return tt_tower_fwd_x(table, n_rows, ids, feats, ldf, B, D, F, hidden, W1, b1, W2, b2, W3, b3, d_out, nullptr, 0, 0, y, ldy,
-                        h_out, tin_out, oob_flag, stream);
-}
-
-extern "C" int tt_tower_bwd_data_x(const float* dy, int64_t ldy, int64_t B, int64_t D, int64_t hidden, const float* W2,
-                                   const float* W3, const float* h, float* d_emb, int64_t ld_demb, float* d_f, float* dh,
-                                   float* d_extra, int64_t ld_dx, int64_t E, tt_stream_t stream) {
-  if (!dy || !W2 || !W3 || !h || !d_emb || !d_f || !dh || (E > 0 && !d_extra)) return fail_arg("tt_tower_bwd_data: null pointer");
-  if (B <= 0 || ldy < D || ld_demb < D || E < 0 || (E > 0 && ld_dx < E)) return fail_arg("tt_tower_bwd_data: sizes");
-  if (!tt_tower_x_supported(D, 1, hidden, D, E) || ldy % 4 || ld_demb % 4 || !al16p(dy) || !al16p(h) || !al16p(d_emb) ||
-      !al16p(d_f) || !al16p(dh) || !al16p(W3) || (E > 0 && (ld_dx % 4 || !al16p(d_extra)))) {
-    set_error("tt_tower_bwd_data: needs hidden = 256, D in {32, 64, 128}, extra width 0 or 2D, 16-B aligned operands");
-    return TT_E_UNSUPPORTED;
-  }
-  TowerBwdArgs a{dy, ldy, B, W2, W3, h, d_emb, ld_demb, d_f, dh, d_extra, ld_dx};
-  hipStream_t st = S(stream);
-  const int rt = tower_row_tiles(B);
-  const unsigned grid = (unsigned)ceil_div(B, 32 * rt);
-#define TT_TWB(E8, X) { if (rt == 1) tower_bwd_kernel<E8, X, 1><<<grid, 256, 0, st>>>(a); else tower_bwd_kernel<E8, X, 2><<<grid, 256, 0, st>>>(a); }
-  if (E == 0) {
-    if (D == 32) TT_TWB(4, false) else if (D == 64) TT_TWB(8, false) else TT_TWB(16, false)
-  } else {
-    if (D == 32) TT_TWB(4, true) else if (D == 64) TT_TWB(8, true) else TT_TWB(16, true)
-  }
-#undef TT_TWB
-  return check_launch("tower_bwd_kernel");
-}
-
-extern "C" int tt_tower_bwd_data(const float* dy, int64_t ldy, int64_t B, int64_t D, int64_t hidden, const float* W2,
-                                 const float* W3, const float* h, float* d_emb, int64_t ld_demb, float* d_f, float* dh,
-                                 tt_stream_t stream) {
-  return tt_tower_bwd_data_x(dy, ldy, B, D, hidden, W2, W3, h, d_emb, ld_demb, d_f, dh, nullptr, 0, 0, stream);
 }
 
 static int64_t tower_part_floats(int64_t D, int64_t F, int64_t E) { return D * (2 * D + E) + D * TW_HID + TW_HID * F + 2 * D + TW_HID; }
 
-extern "C" int64_t tt_tower_bwd_weights_x_workspace_bytes(int64_t B, int64_t D, int64_t F, int64_t hidden, int64_t E) {
-  if (B <= 0 || !tt_tower_x_supported(D, F, hidden, D, E)) return 256;
+extern "C" int64_t tt_tower_bwd_weights_workspace_bytes(int64_t B, int64_t D, int64_t F, int64_t hidden, int64_t E) {
+  if (B <= 0 || !tt_tower_supported(D, F, hidden, D, E)) return 256;
   return round_up(ceil_div(B, TW_ROWS) * tower_part_floats(D, F, E) * (int64_t)sizeof(float), 256);
 }
-extern "C" int64_t tt_tower_bwd_weights_workspace_bytes(int64_t B, int64_t D, int64_t F, int64_t hidden) {
-  return tt_tower_bwd_weights_x_workspace_bytes(B, D, F, hidden, 0);
-}
 
-extern "C" int tt_tower_bwd_weights_x(const float* dy, int64_t ldy, const float* tin, const float* d_f, const float* h,
-                                      const float* dh, const float* feats, int64_t ldf, const float* extra, int64_t ldx,
-                                      int64_t E, int64_t B, int64_t D, int64_t F, int64_t hidden, float* dW1, float* db1,
-                                      float* dW2, float* db2, float* dW3, float* db3, void* ws, int64_t ws_bytes,
-                                      tt_stream_t stream) {
-  if (!dy || !tin || !d_f || !h || !dh || !feats || !dW1 || !db1 || !dW2 || !db2 || !dW3 || !db3 || !ws || (E > 0 && !extra))
-    return fail_arg("tt_tower_bwd_weights: null pointer");
-  if (B <= 0 || ldy < D || ldf < F || E < 0 || (E > 0 && ldx < E)) return fail_arg("tt_tower_bwd_weights: sizes");
-  if (!tt_tower_x_supported(D, F, hidden, D, E) || ldy % 4 || !al16p(dy) || !al16p(tin) || !al16p(d_f) || !al16p(h) ||
-      !al16p(dh) || (E > 0 && (ldx % 4 || !al16p(extra)))) {
-    set_error("tt_tower_bwd_weights: needs hidden = 256, D in {32, 64, 128}, F <= 64, extra width 0 or 2D, 16-B aligned operands");
-    return TT_E_UNSUPPORTED;
+// ---------------------------------------------------------------- argument checks: the call, then each side
+static int tower_call_check(const char* who, const void* sides, int32_t n_sides, int64_t B, int64_t E) {
+  if (!sides || n_sides < 1 || n_sides > 2 || B <= 0 || E < 0) {
+    set_error("bad argument: %s: needs sides, n_sides = 1 or 2, B > 0, E >= 0", who);
+    return TT_E_BADARG;
   }
-  if (ws_bytes < tt_tower_bwd_weights_x_workspace_bytes(B, D, F, hidden, E)) { set_error("tt_tower_bwd_weights: workspace"); return TT_E_WORKSPACE; }
-  TowerWgradArgs a{dy, ldy, tin, d_f, h, dh, feats, ldf, F, B, reinterpret_cast<float*>(ws), extra, ldx};
-  hipStream_t st = S(stream);
-  const unsigned grid = (unsigned)ceil_div(B, TW_ROWS);
-  const size_t lds = (size_t)(TW_ROWS * D + TW_ROWS * TW_HID + TW_ROWS * F) * sizeof(float);
-#define TT_TWG(E8, X)                                                                                                    \
-  {                                                                                                                      \
-    if (lds > 64 * 1024) {                                                                                               \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_wgrad_kernel<E8, X>),                      \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-      if (e != hipSuccess) { set_error("tower_wgrad_kernel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; } \
-    }                                                                                                                    \
-    tower_wgrad_kernel<E8, X><<<grid, 256, lds, st>>>(a);                                                                \
-  }
-  if (E == 0) {
-    if (D == 32) TT_TWG(4, false) else if (D == 64) TT_TWG(8, false) else TT_TWG(16, false)
-  } else {
-    if (D == 32) TT_TWG(4, true) else if (D == 64) TT_TWG(8, true) else TT_TWG(16, true)
-  }
-#undef TT_TWG
-  int rc = check_launch("tower_wgrad_kernel");
-  if (rc) return rc;
-  const int64_t n3 = D * (2 * D + E), n2 = D * TW_HID, n1 = TW_HID * F, part = tower_part_floats(D, F, E);
-  tower_wgrad_reduce_kernel<<<(unsigned)ceil_div(part, 64), 1024, 0, st>>>(reinterpret_cast<const float*>(ws), (int)grid, part, n3, n2,
-                                                                           n1, D, dW3, dW2, dW1, db3, db2, db1);
-  return check_launch("tower_wgrad_reduce_kernel");
-}
-
-extern "C" int tt_tower_bwd_weights(const float* dy, int64_t ldy, const float* tin, const float* d_f, const float* h,
-                                    const float* dh, const float* feats, int64_t ldf, int64_t B, int64_t D, int64_t F,
-                                    int64_t hidden, float* dW1, float* db1, float* dW2, float* db2, float* dW3, float* db3,
-                                    void* ws, int64_t ws_bytes, tt_stream_t stream) {
-  return tt_tower_bwd_weights_x(dy, ldy, tin, d_f, h, dh, feats, ldf, nullptr, 0, 0, B, D, F, hidden, dW1, db1, dW2, db2, dW3, db3,
-                                ws, ws_bytes, stream);
-}
-
-// ---------------------------------------------------------------- both towers of the base model per launch
-static int pair_shape_check(const char* who, int64_t B, int64_t D, int64_t hidden, int64_t F0, int64_t F1) {
-  if (B <= 0) return fail_arg(who);
-  if (!tower_shape_ok(D, F0, hidden, D) || !tower_shape_ok(D, F1, hidden, D)) {
-    set_error("%s: needs hidden = 256, D in {32, 64, 128} (the same for both towers), F <= 64", who);
+  if (n_sides == 2 && E != 0) {  // the *_pair_kernels have no third input block
+    set_error("%s: two sides take no third input block", who);
     return TT_E_UNSUPPORTED;
   }
   return 0;
 }
 
-extern "C" int tt_tower_fwd_pair(const tt_tower_fwd_side* sides, int64_t B, int64_t D, int64_t hidden, int32_t* oob_flag,
-                                 tt_stream_t stream) {
-  if (!sides) return fail_arg("tt_tower_fwd_pair: null pointer");
-  int rc = pair_shape_check("tt_tower_fwd_pair", B, D, hidden, sides[0].F, sides[1].F);
-  if (rc) return rc;
+static int tower_fwd_side_check(const tt_tower_fwd_side& s, int64_t D, int64_t hidden, int64_t E) {
+  if (!s.table || !s.ids || !s.feats || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.W3 || !s.b3 || !s.y || !s.h_out || !s.tin_out ||
+      (E > 0 && !s.extra))
+    return fail_arg("tt_tower_fwd: null pointer");
+  if (s.n_rows <= 0 || s.ldf < s.F || s.ldy < D || (E > 0 && s.ldx < E)) return fail_arg("tt_tower_fwd: sizes");
+  if (!tt_tower_supported(D, s.F, hidden, D, E) || s.ldy % 4 || !al16p(s.table) || !al16p(s.W2) || !al16p(s.W3) || !al16p(s.y) ||
+      !al16p(s.h_out) || !al16p(s.tin_out) || (E > 0 && (s.ldx % 4 || !al16p(s.extra)))) {
+    set_error("tt_tower_fwd: needs hidden = 256, D in {32, 64, 128}, F <= 64, extra width 0 or 2D, 16-B aligned operands");
+    return TT_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
+static int tower_bwd_side_check(const tt_tower_bwd_side& s, int64_t D, int64_t hidden, int64_t E) {
+  if (!s.dy || !s.W2 || !s.W3 || !s.h || !s.d_emb || !s.d_f || !s.dh || (E > 0 && !s.d_extra))
+    return fail_arg("tt_tower_bwd_data: null pointer");
+  if (s.ldy < D || s.ld_demb < D || (E > 0 && s.ld_dx < E)) return fail_arg("tt_tower_bwd_data: sizes");
+  if (!tt_tower_supported(D, 1, hidden, D, E) || s.ldy % 4 || s.ld_demb % 4 || !al16p(s.dy) || !al16p(s.h) || !al16p(s.d_emb) ||
+      !al16p(s.d_f) || !al16p(s.dh) || !al16p(s.W3) || (E > 0 && (s.ld_dx % 4 || !al16p(s.d_extra)))) {
+    set_error("tt_tower_bwd_data: needs hidden = 256, D in {32, 64, 128}, extra width 0 or 2D, 16-B aligned operands");
+    return TT_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
+static int tower_wgrad_side_check(const tt_tower_wgrad_side& s, int64_t B, int64_t D, int64_t hidden, int64_t E) {
+  if (!s.dy || !s.tin || !s.d_f || !s.h || !s.dh || !s.feats || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 || !s.dW3 || !s.db3 || !s.ws ||
+      (E > 0 && !s.extra))
+    return fail_arg("tt_tower_bwd_weights: null pointer");
+  if (s.ldy < D || s.ldf < s.F || (E > 0 && s.ldx < E)) return fail_arg("tt_tower_bwd_weights: sizes");
+  if (!tt_tower_supported(D, s.F, hidden, D, E) || s.ldy % 4 || !al16p(s.dy) || !al16p(s.tin) || !al16p(s.d_f) || !al16p(s.h) ||
+      !al16p(s.dh) || (E > 0 && (s.ldx % 4 || !al16p(s.extra)))) {
+    set_error("tt_tower_bwd_weights: needs hidden = 256, D in {32, 64, 128}, F <= 64, extra width 0 or 2D, 16-B aligned operands");
+    return TT_E_UNSUPPORTED;
+  }
+  if (s.ws_bytes < tt_tower_bwd_weights_workspace_bytes(B, D, s.F, hidden, E)) { set_error("tt_tower_bwd_weights: workspace"); return TT_E_WORKSPACE; }
+  return 0;
+}
+
+// ---------------------------------------------------------------- launches
+// One 256-thread launch; dynamic LDS above 64 KB has to be granted to the kernel first.
+template <typename Args>
+static int tower_launch(void (*kernel)(Args), const char* name, dim3 grid, size_t lds, hipStream_t st, const Args& a) {
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e)); return (int)e; }
+  }
+  kernel<<<grid, 256, lds, st>>>(a);
+  return check_launch(name);
+}
+
+// The kernel of a launch from the runtime shape: E8 = D / 8, X = a third input block, R = tower_row_tiles(B).  One
+// function per kernel family, in this order: it is the order the kernels are instantiated in, and so the order of the
+// device code.
+static int tower_fwd_one(const TowerFwdArgs& a, int64_t D, int64_t E, int rt, dim3 grid, size_t lds, hipStream_t st) {
+#define TT_L(E8, X) (rt == 1 ? tower_launch(tower_fwd_kernel<E8, X, 1>, "tower_fwd_kernel", grid, lds, st, a) \
+                             : tower_launch(tower_fwd_kernel<E8, X, 2>, "tower_fwd_kernel", grid, lds, st, a))
+  if (E == 0) return D == 32 ? TT_L(4, false) : D == 64 ? TT_L(8, false) : TT_L(16, false);
+  return D == 32 ? TT_L(4, true) : D == 64 ? TT_L(8, true) : TT_L(16, true);
+#undef TT_L
+}
+static int tower_bwd_one(const TowerBwdArgs& a, int64_t D, int64_t E, int rt, dim3 grid, hipStream_t st) {
+#define TT_L(E8, X) (rt == 1 ? tower_launch(tower_bwd_kernel<E8, X, 1>, "tower_bwd_kernel", grid, 0, st, a) \
+                             : tower_launch(tower_bwd_kernel<E8, X, 2>, "tower_bwd_kernel", grid, 0, st, a))
+  if (E == 0) return D == 32 ? TT_L(4, false) : D == 64 ? TT_L(8, false) : TT_L(16, false);
+  return D == 32 ? TT_L(4, true) : D == 64 ? TT_L(8, true) : TT_L(16, true);
+#undef TT_L
+}
+static int tower_wgrad_one(const TowerWgradArgs& a, int64_t D, int64_t E, dim3 grid, size_t lds, hipStream_t st) {
+#define TT_L(E8, X) tower_launch(tower_wgrad_kernel<E8, X>, "tower_wgrad_kernel", grid, lds, st, a)
+  if (E == 0) return D == 32 ? TT_L(4, false) : D == 64 ? TT_L(8, false) : TT_L(16, false);
+  return D == 32 ? TT_L(4, true) : D == 64 ? TT_L(8, true) : TT_L(16, true);
+#undef TT_L
+}
+static int tower_fwd_two(const TowerFwdArgs2& q, int64_t D, int rt, dim3 grid, size_t lds, hipStream_t st) {
+#define TT_L(E8) (rt == 1 ? tower_launch(tower_fwd_pair_kernel<E8, 1>, "tower_fwd_pair_kernel", grid, lds, st, q) \
+                          : tower_launch(tower_fwd_pair_kernel<E8, 2>, "tower_fwd_pair_kernel", grid, lds, st, q))
+  return D == 32 ? TT_L(4) : D == 64 ? TT_L(8) : TT_L(16);
+#undef TT_L
+}
+static int tower_bwd_two(const TowerBwdArgs2& q, int64_t D, int rt, dim3 grid, hipStream_t st) {
+#define TT_L(E8) (rt == 1 ? tower_launch(tower_bwd_pair_kernel<E8, 1>, "tower_bwd_pair_kernel", grid, 0, st, q) \
+                          : tower_launch(tower_bwd_pair_kernel<E8, 2>, "tower_bwd_pair_kernel", grid, 0, st, q))
+  return D == 32 ? TT_L(4) : D == 64 ? TT_L(8) : TT_L(16);
+#undef TT_L
+}
+static int tower_wgrad_two(const TowerWgradArgs2& q, int64_t D, dim3 grid, size_t lds, hipStream_t st) {
+#define TT_L(E8) tower_launch(tower_wgrad_pair_kernel<E8>, "tower_wgrad_pair_kernel", grid, lds, st, q)
+  return D == 32 ? TT_L(4) : D == 64 ? TT_L(8) : TT_L(16);
+#undef TT_L
+}
+
+// ---------------------------------------------------------------- entry points: one tower, or both towers of the base model
+extern "C" int tt_tower_fwd(const tt_tower_fwd_side* sides, int32_t n_sides, int64_t B, int64_t D, int64_t hidden, int64_t E,
+                            int32_t* oob_flag, tt_stream_t stream) {
+  if (int rc = tower_call_check("tt_tower_fwd", sides, n_sides, B, E)) return rc;
   TowerFwdArgs2 q{};
   int64_t Fmax = 0;
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < n_sides; ++k) {
     const tt_tower_fwd_side& s = sides[k];
-    if (!s.table || !s.ids || !s.feats || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.W3 || !s.b3 || !s.y || !s.h_out || !s.tin_out)
-      return fail_arg("tt_tower_fwd_pair: null pointer");
-    if (s.n_rows <= 0 || s.ldf < s.F || s.ldy < D) return fail_arg("tt_tower_fwd_pair: sizes");
-    if (s.ldy % 4 || !al16p(s.table) || !al16p(s.W2) || !al16p(s.W3) || !al16p(s.y) || !al16p(s.h_out) || !al16p(s.tin_out)) {
-      set_error("tt_tower_fwd_pair: 16-B aligned operands");
-      return TT_E_UNSUPPORTED;
-    }
+    if (int rc = tower_fwd_side_check(s, D, hidden, E)) return rc;
     q.t[k] = TowerFwdArgs{s.table, s.n_rows, s.ids, s.feats, s.ldf, B, s.F, s.W1, s.b1, s.W2, s.b2, s.W3, s.b3, s.y, s.ldy,
-                          s.h_out, s.tin_out, oob_flag, nullptr, 0};
+                          s.h_out, s.tin_out, oob_flag, s.extra, s.ldx};
     Fmax = s.F > Fmax ? s.F : Fmax;
   }
   hipStream_t st = S(stream);
   const int rt = tower_row_tiles(B);
   const int rows = 32 * rt;
-  const dim3 grid((unsigned)ceil_div(B, rows), 2);
+  const dim3 grid((unsigned)ceil_div(B, rows), (unsigned)n_sides);
   const size_t lds = (size_t)(rows * (TW_HID + 4) + rows * (2 * D + 4) + rows * Fmax) * sizeof(float);
-#define TT_TWP1(E8, R)                                                                                                   \
-  {                                                                                                                      \
-    if (lds > 64 * 1024) {                                                                                               \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_fwd_pair_kernel<E8, R>),                   \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-      if (e != hipSuccess) { set_error("tower_fwd_pair_kernel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; } \
-    }                                                                                                                    \
-    tower_fwd_pair_kernel<E8, R><<<grid, 256, lds, st>>>(q);                                                             \
-  }
-#define TT_TWP(E8) { if (rt == 1) TT_TWP1(E8, 1) else TT_TWP1(E8, 2) }
-  if (D == 32) TT_TWP(4) else if (D == 64) TT_TWP(8) else TT_TWP(16)
-#undef TT_TWP
-#undef TT_TWP1
-  return check_launch("tower_fwd_pair_kernel");
+  return n_sides == 1 ? tower_fwd_one(q.t[0], D, E, rt, grid, lds, st) : tower_fwd_two(q, D, rt, grid, lds, st);
 }
 
-extern "C" int tt_tower_bwd_data_pair(const tt_tower_bwd_side* sides, int64_t B, int64_t D, int64_t hidden, tt_stream_t stream) {
-  if (!sides) return fail_arg("tt_tower_bwd_data_pair: null pointer");
-  int rc = pair_shape_check("tt_tower_bwd_data_pair", B, D, hidden, 1, 1);
-  if (rc) return rc;
+extern "C" int tt_tower_bwd_data(const tt_tower_bwd_side* sides, int32_t n_sides, int64_t B, int64_t D, int64_t hidden, int64_t E,
+                                 tt_stream_t stream) {
+  if (int rc = tower_call_check("tt_tower_bwd_data", sides, n_sides, B, E)) return rc;
   TowerBwdArgs2 q{};
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < n_sides; ++k) {
     const tt_tower_bwd_side& s = sides[k];
-    if (!s.dy || !s.W2 || !s.W3 || !s.h || !s.d_emb || !s.d_f || !s.dh) return fail_arg("tt_tower_bwd_data_pair: null pointer");
-    if (s.ldy < D || s.ld_demb < D) return fail_arg("tt_tower_bwd_data_pair: sizes");
-    if (s.ldy % 4 || s.ld_demb % 4 || !al16p(s.dy) || !al16p(s.h) || !al16p(s.d_emb) || !al16p(s.d_f) || !al16p(s.dh) || !al16p(s.W3)) {
-      set_error("tt_tower_bwd_data_pair: 16-B aligned operands");
-      return TT_E_UNSUPPORTED;
-    }
-    q.t[k] = TowerBwdArgs{s.dy, s.ldy, B, s.W2, s.W3, s.h, s.d_emb, s.ld_demb, s.d_f, s.dh, nullptr, 0};
+    if (int rc = tower_bwd_side_check(s, D, hidden, E)) return rc;
+    q.t[k] = TowerBwdArgs{s.dy, s.ldy, B, s.W2, s.W3, s.h, s.d_emb, s.ld_demb, s.d_f, s.dh, s.d_extra, s.ld_dx};
   }
   hipStream_t st = S(stream);
   const int rt = tower_row_tiles(B);
-  const dim3 grid((unsigned)ceil_div(B, 32 * rt), 2);
-#define TT_TBP(E8) { if (rt == 1) tower_bwd_pair_kernel<E8, 1><<<grid, 256, 0, st>>>(q); else tower_bwd_pair_kernel<E8, 2><<<grid, 256, 0, st>>>(q); }
-  if (D == 32) TT_TBP(4) else if (D == 64) TT_TBP(8) else TT_TBP(16)
-#undef TT_TBP
-  return check_launch("tower_bwd_pair_kernel");
+  const dim3 grid((unsigned)ceil_div(B, 32 * rt), (unsigned)n_sides);
+  return n_sides == 1 ? tower_bwd_one(q.t[0], D, E, rt, grid, st) : tower_bwd_two(q, D, rt, grid, st);
 }
 
-extern "C" int tt_tower_bwd_weights_pair(const tt_tower_wgrad_side* sides, int64_t B, int64_t D, int64_t hidden, tt_stream_t stream) {
-  if (!sides) return fail_arg("tt_tower_bwd_weights_pair: null pointer");
-  int rc = pair_shape_check("tt_tower_bwd_weights_pair", B, D, hidden, sides[0].F, sides[1].F);
-  if (rc) return rc;
+extern "C" int tt_tower_bwd_weights(const tt_tower_wgrad_side* sides, int32_t n_sides, int64_t B, int64_t D, int64_t hidden,
+                                    int64_t E, tt_stream_t stream) {
+  if (int rc = tower_call_check("tt_tower_bwd_weights", sides, n_sides, B, E)) return rc;
   TowerWgradArgs2 q{};
   TowerReduceArgs2 r{};
   int64_t Fmax = 0, part_max = 0;
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < n_sides; ++k) {
     const tt_tower_wgrad_side& s = sides[k];
-    if (!s.dy || !s.tin || !s.d_f || !s.h || !s.dh || !s.feats || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 || !s.dW3 || !s.db3 || !s.ws)
-      return fail_arg("tt_tower_bwd_weights_pair: null pointer");
-    if (s.ldy < D || s.ldf < s.F) return fail_arg("tt_tower_bwd_weights_pair: sizes");
-    if (s.ldy % 4 || !al16p(s.dy) || !al16p(s.tin) || !al16p(s.d_f) || !al16p(s.h) || !al16p(s.dh)) {
-      set_error("tt_tower_bwd_weights_pair: 16-B aligned operands");
-      return TT_E_UNSUPPORTED;
-    }
-    if (s.ws_bytes < tt_tower_bwd_weights_x_workspace_bytes(B, D, s.F, hidden, 0)) { set_error("tt_tower_bwd_weights_pair: workspace"); return TT_E_WORKSPACE; }
-    q.t[k] = TowerWgradArgs{s.dy, s.ldy, s.tin, s.d_f, s.h, s.dh, s.feats, s.ldf, s.F, B, reinterpret_cast<float*>(s.ws), nullptr, 0};
+    if (int rc = tower_wgrad_side_check(s, B, D, hidden, E)) return rc;
+    q.t[k] = TowerWgradArgs{s.dy, s.ldy, s.tin, s.d_f, s.h, s.dh, s.feats, s.ldf, s.F, B, reinterpret_cast<float*>(s.ws), s.extra, s.ldx};
     r.part[k] = reinterpret_cast<const float*>(s.ws);
-    r.part_floats[k] = tower_part_floats(D, s.F, 0);
-    r.n3[k] = D * 2 * D; r.n2[k] = D * TW_HID; r.n1[k] = TW_HID * s.F;
+    r.part_floats[k] = tower_part_floats(D, s.F, E);
+    r.n3[k] = D * (2 * D + E); r.n2[k] = D * TW_HID; r.n1[k] = TW_HID * s.F;
     r.dW3[k] = s.dW3; r.dW2[k] = s.dW2; r.dW1[k] = s.dW1; r.db3[k] = s.db3; r.db2[k] = s.db2; r.db1[k] = s.db1;
     Fmax = s.F > Fmax ? s.F : Fmax;
     part_max = r.part_floats[k] > part_max ? r.part_floats[k] : part_max;
   }
   hipStream_t st = S(stream);
   const unsigned blocks = (unsigned)ceil_div(B, TW_ROWS);
+  const dim3 grid(blocks, (unsigned)n_sides);
   const size_t lds = (size_t)(TW_ROWS * D + TW_ROWS * TW_HID + TW_ROWS * Fmax) * sizeof(float);
-#define TT_TGP(E8)                                                                                                       \
-  {                                                                                                                      \
-    if (lds > 64 * 1024) {                                                                                               \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_wgrad_pair_kernel<E8>),                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-      if (e != hipSuccess) { set_error("tower_wgrad_pair_kernel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; } \
-    }                                                                                                                    \
-    tower_wgrad_pair_kernel<E8><<<dim3(blocks, 2), 256, lds, st>>>(q);                                                   \
+  const unsigned reduce_blocks = (unsigned)ceil_div(part_max, 64);
+  if (n_sides == 1) {
+    if (int rc = tower_wgrad_one(q.t[0], D, E, grid, lds, st)) return rc;
+    tower_wgrad_reduce_kernel<<<reduce_blocks, 1024, 0, st>>>(r.part[0], (int)blocks, r.part_floats[0], r.n3[0], r.n2[0], r.n1[0], D,
+                                                              r.dW3[0], r.dW2[0], r.dW1[0], r.db3[0], r.db2[0], r.db1[0]);
+    return check_launch("tower_wgrad_reduce_kernel");
   }
-  if (D == 32) TT_TGP(4) else if (D == 64) TT_TGP(8) else TT_TGP(16)
-#undef TT_TGP
-  rc = check_launch("tower_wgrad_pair_kernel");
-  if (rc) return rc;
-  tower_wgrad_reduce_pair_kernel<<<dim3((unsigned)ceil_div(part_max, 64), 2), 1024, 0, st>>>(r, (int)blocks, D);
+  if (int rc = tower_wgrad_two(q, D, grid, lds, st)) return rc;
+  tower_wgrad_reduce_pair_kernel<<<dim3(reduce_blocks, 2), 1024, 0, st>>>(r, (int)blocks, D);
   return check_launch("tower_wgrad_reduce_pair_kernel");
 }

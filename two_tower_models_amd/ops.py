@@ -674,18 +674,80 @@ class TowerInput(_LookupFunction):
 
 
 def fused_tower_supported(weight, feats, W1, W2, W3, extra_width: int = 0) -> bool:
-    """tt_tower_fwd(_x) / tt_tower_bwd_data(_x): hidden = 256, D = d_out in {32, 64, 128}, F <= 64; a third input
+    """tt_tower_fwd / tt_tower_bwd_data: hidden = 256, D = d_out in {32, 64, 128}, F <= 64; a third input
     block (`extra_width` columns: the history model's [recent | mean] summary) must be 2D wide."""
     if not (weight.is_cuda and feats.dim() == 2 and feats.dtype == torch.float32):
         return False
     ok = (W3.shape[1] == 2 * weight.shape[1] + extra_width and W2.shape[0] == weight.shape[1]
-          and bool(N.load().tt_tower_x_supported(weight.shape[1], feats.shape[1], W1.shape[0], W3.shape[0], extra_width)))
+          and bool(N.load().tt_tower_supported(weight.shape[1], feats.shape[1], W1.shape[0], W3.shape[0], extra_width)))
     if not ok:
         note_generic("tower (id lookup + feature MLP + tower Linear)",
                      f"the fused kernel takes hidden = 256, D = d_out in {{32, 64, 128}}, F <= 64, a third input block of 0 or 2D "
                      f"columns; got hidden = {W1.shape[0]}, D = {weight.shape[1]}, d_out = {W3.shape[0]}, F = {feats.shape[1]}, "
                      f"third block {extra_width}: gather + three GEMM launches per direction")
     return ok
+
+
+def _tower_fwd_side(recording, weight, ids, feats, W1, b1, W2, b2, W3, b3, extra=None):
+    """One tower's tt_tower_fwd_side -> (side, y, saved, lookup index, keep): the output it writes, what the backward takes
+    (ids, feats, h, tin, W2, W3) and the packed inputs it points into (alive until the launch is queued)."""
+    dev = weight.device
+    feats = _rowmajor(feats)
+    B, F = feats.shape
+    D, Hd = weight.shape[1], W1.shape[0]
+    if ids.dtype == torch.int32:
+        ids = ids.to(torch.int64)
+    if ids.dtype != torch.int64:
+        raise TypeError("ids must be int64 or int32 (nn.Embedding's index types)")
+    src, row_ids, index = lookup_source(weight, ids, recording)
+    row_ids = row_ids.contiguous()
+    y = torch.empty(B, W3.shape[0], dtype=torch.float32, device=dev)
+    h = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    tin = torch.empty(B, 2 * D, dtype=torch.float32, device=dev)
+    W1c, W2c, W3c = W1.contiguous(), W2.contiguous(), W3.contiguous()
+    sd = N.TowerFwdSide()
+    sd.table, sd.n_rows, sd.ids, sd.feats, sd.ldf, sd.F = src.data_ptr(), src.shape[0], row_ids.data_ptr(), feats.data_ptr(), feats.stride(0), F
+    sd.W1, sd.b1, sd.W2, sd.b2, sd.W3, sd.b3 = W1c.data_ptr(), b1.data_ptr(), W2c.data_ptr(), b2.data_ptr(), W3c.data_ptr(), b3.data_ptr()
+    sd.y, sd.ldy, sd.h_out, sd.tin_out = y.data_ptr(), y.stride(0), h.data_ptr(), tin.data_ptr()
+    if extra is not None:
+        sd.extra, sd.ldx = extra.data_ptr(), extra.stride(0)
+    return sd, y, (ids, feats, h, tin, W2c, W3c), index, (src, row_ids, W1c)
+
+
+def _tower_bwd_side(dy, h, W2, W3, E=0):
+    """One tower's tt_tower_bwd_side -> (side, d_emb, d_f, dh, d_extra): the gradients it writes."""
+    dev = dy.device
+    B, D = dy.shape
+    d_emb = torch.empty(B, D, dtype=torch.float32, device=dev)
+    d_f = torch.empty(B, D, dtype=torch.float32, device=dev)
+    dh = torch.empty(B, h.shape[1], dtype=torch.float32, device=dev)
+    d_extra = torch.empty(B, E, dtype=torch.float32, device=dev) if E else None
+    sd = N.TowerBwdSide()
+    sd.dy, sd.ldy, sd.W2, sd.W3, sd.h = dy.data_ptr(), dy.stride(0), W2.data_ptr(), W3.data_ptr(), h.data_ptr()
+    sd.d_emb, sd.ld_demb, sd.d_f, sd.dh = d_emb.data_ptr(), D, d_f.data_ptr(), dh.data_ptr()
+    sd.d_extra, sd.ld_dx = N.ptr(d_extra), E
+    return sd, d_emb, d_f, dh, d_extra
+
+
+def _tower_grads(dev, D, Hd, F, E=0):
+    """Empty (dW1, db1, dW2, db2, dW3, db3) of one tower."""
+    return tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ((Hd, F), (Hd,), (D, Hd), (D,), (D, 2 * D + E), (D,)))
+
+
+def _tower_wgrad_side(dy, tin, d_f, h, dh, feats, grads, slot, extra=None):
+    """One tower's tt_tower_wgrad_side: the six gradients into `grads` (dW1, db1, dW2, db2, dW3, db3), the blocks'
+    partials into scratch slot `slot`."""
+    B, D = dy.shape
+    Hd, F = h.shape[1], feats.shape[1]
+    E = 0 if extra is None else extra.shape[1]
+    sd = N.TowerWgradSide()
+    sd.dy, sd.ldy, sd.tin, sd.d_f, sd.h, sd.dh = dy.data_ptr(), dy.stride(0), tin.data_ptr(), d_f.data_ptr(), h.data_ptr(), dh.data_ptr()
+    sd.feats, sd.ldf, sd.F = feats.data_ptr(), feats.stride(0), F
+    sd.dW1, sd.db1, sd.dW2, sd.db2, sd.dW3, sd.db3 = (g.data_ptr() for g in grads)
+    sd.ws, sd.ws_bytes = _ws(dy.device, N.load().tt_tower_bwd_weights_workspace_bytes(B, D, F, Hd, E), slot)
+    if extra is not None:
+        sd.extra, sd.ldx = extra.data_ptr(), extra.stride(0)
+    return sd
 
 
 class FusedTower(_LookupFunction):
@@ -697,36 +759,21 @@ class FusedTower(_LookupFunction):
     @staticmethod
     def forward(ctx, weight, ids, feats, W1, b1, W2, b2, W3, b3, extra=None):
         dev = N.require_device(weight, ids, feats, W1, b1, W2, b2, W3, b3)
-        feats = _rowmajor(feats)
         if extra is not None:
             N.require_device(extra)
             extra = _rowmajor(extra)
-            # tt_tower_*_x read the third block with 16-byte loads: an encoder that returns an offset / oddly strided view
+            # tt_tower_* read the third block with 16-byte loads: an encoder that returns an offset / oddly strided view
             # (a user-supplied module may) gets a packed copy instead of TT_E_UNSUPPORTED
             if extra.data_ptr() % 16 or extra.stride(0) % 4:
                 extra = extra.contiguous()
         E = 0 if extra is None else extra.shape[1]
-        B, F = feats.shape
-        D, Hd = weight.shape[1], W1.shape[0]
-        if ids.dtype == torch.int32:
-            ids = ids.to(torch.int64)
-        if ids.dtype != torch.int64:
-            raise TypeError("ids must be int64 or int32 (nn.Embedding's index types)")
-        src, row_ids, ctx.lookup_index = lookup_source(weight, ids, _recording(ctx))
-        row_ids = row_ids.contiguous()
-        y = torch.empty(B, W3.shape[0], dtype=torch.float32, device=dev)
-        h = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        tin = torch.empty(B, 2 * D, dtype=torch.float32, device=dev)
-        W1c, W2c, W3c = W1.contiguous(), W2.contiguous(), W3.contiguous()
-        N.check(N.load().tt_tower_fwd_x(src.data_ptr(), src.shape[0], row_ids.data_ptr(), feats.data_ptr(), feats.stride(0), B, D,
-                                        F, Hd, W1c.data_ptr(), b1.data_ptr(), W2c.data_ptr(), b2.data_ptr(), W3c.data_ptr(),
-                                        b3.data_ptr(), W3.shape[0], N.ptr(extra), extra.stride(0) if E else 0, E,
-                                        y.data_ptr(), y.stride(0), h.data_ptr(), tin.data_ptr(),
-                                        N.oob.flag(dev).data_ptr(), N.stream()), "tt_tower_fwd_x")
+        sd, y, saved, ctx.lookup_index, keep = _tower_fwd_side(_recording(ctx), weight, ids, feats, W1, b1, W2, b2, W3, b3, extra)
+        N.check(N.load().tt_tower_fwd(sd, 1, y.shape[0], weight.shape[1], W1.shape[0], E, N.oob.flag(dev).data_ptr(), N.stream()),
+                "tt_tower_fwd")
         ctx.weight = weight
         ctx.has_extra = extra is not None
         ctx.tower_leaves = (W1, b1, W2, b2, W3, b3)  # as passed in: the Parameters (ops.run_on_side: `leaves`)
-        ctx.save_for_backward(ids, feats, h, tin, W2c, W3c, *(() if extra is None else (extra,)))
+        ctx.save_for_backward(*saved, *(() if extra is None else (extra,)))
         return y
 
     @staticmethod
@@ -740,17 +787,9 @@ class FusedTower(_LookupFunction):
         dy = dy.contiguous()
         B, F = feats.shape
         D, Hd = w.shape[1], h.shape[1]
-        d_emb = torch.empty(B, D, dtype=torch.float32, device=dev)
-        d_f = torch.empty(B, D, dtype=torch.float32, device=dev)
-        dh = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        d_extra = torch.empty(B, E, dtype=torch.float32, device=dev) if E else None
-        N.check(N.load().tt_tower_bwd_data_x(dy.data_ptr(), dy.stride(0), B, D, Hd, W2.data_ptr(), W3.data_ptr(), h.data_ptr(),
-                                             d_emb.data_ptr(), D, d_f.data_ptr(), dh.data_ptr(), N.ptr(d_extra), E, E,
-                                             N.stream()), "tt_tower_bwd_data_x")
-        E3 = 0 if extra is None else extra.shape[1]
-        outs = (torch.empty(Hd, F, dtype=torch.float32, device=dev), torch.empty(Hd, dtype=torch.float32, device=dev),
-                torch.empty(D, Hd, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev),
-                torch.empty(D, 2 * D + E3, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev))
+        sd, d_emb, d_f, dh, d_extra = _tower_bwd_side(dy, h, W2, W3, E)
+        N.check(N.load().tt_tower_bwd_data(sd, 1, B, D, Hd, E, N.stream()), "tt_tower_bwd_data")
+        outs = _tower_grads(dev, D, Hd, F, E)
         # (the towers' weight gradients go to the third stream only in a step that also runs the history encoder -- there
         # they are worth 0.1 ms of the 4.3 ms C3 step, underneath the encoder's backward; in the sweep-bound base model the
         # extra stream hop COSTS 0.06 ms of the 1.15 ms C2 step)
@@ -769,45 +808,28 @@ class FusedTower(_LookupFunction):
 
 
 class FusedTowerPair(_LookupFunction):
-    """FusedTower for BOTH towers of the base model with one launch per direction (tt_tower_*_pair: blockIdx.y picks the
+    """FusedTower for BOTH towers of the base model with one launch per direction (tt_tower_* with two sides: blockIdx.y picks the
     tower; the kernels' bodies are FusedTower's, so the bits are too).  For steps that run on ONE stream -- a whole-step
     hipGraph, batches too small for the two-stream fork -- where one tower's 128 workgroups left half the chip idle twice in
     a row.  Inputs: the user tower's nine FusedTower arguments, then the item tower's; returns (user_emb, item_emb)."""
 
     @staticmethod
     def forward(ctx, *args):
-        u, i = args[:9], args[9:]
         dev = N.require_device(*args)
-        lib = N.load()
         sides = (N.TowerFwdSide * 2)()
         keep, saved, outs = [], [], []
         ctx.lookup_index, ctx.tower_weight = [], []
         caller_grad = _caller_grad_mode[0]
-        for k, (weight, ids, feats, W1, b1, W2, b2, W3, b3) in enumerate((u, i)):
-            feats = _rowmajor(feats)
-            B, F = feats.shape
-            D, Hd = weight.shape[1], W1.shape[0]
-            if ids.dtype == torch.int32:
-                ids = ids.to(torch.int64)
-            if ids.dtype != torch.int64:
-                raise TypeError("ids must be int64 or int32 (nn.Embedding's index types)")
+        for k, (weight, ids, feats, W1, b1, W2, b2, W3, b3) in enumerate((args[:9], args[9:])):
             recording = bool(ctx.needs_input_grad[9 * k]) and caller_grad
-            src, row_ids, idx = lookup_source(weight, ids, recording)
-            row_ids = row_ids.contiguous()
-            y = torch.empty(B, W3.shape[0], dtype=torch.float32, device=dev)
-            h = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-            tin = torch.empty(B, 2 * D, dtype=torch.float32, device=dev)
-            W1c, W2c, W3c = W1.contiguous(), W2.contiguous(), W3.contiguous()
-            sd = sides[k]
-            sd.table, sd.n_rows, sd.ids, sd.feats, sd.ldf, sd.F = src.data_ptr(), src.shape[0], row_ids.data_ptr(), feats.data_ptr(), feats.stride(0), F
-            sd.W1, sd.b1, sd.W2, sd.b2, sd.W3, sd.b3 = W1c.data_ptr(), b1.data_ptr(), W2c.data_ptr(), b2.data_ptr(), W3c.data_ptr(), b3.data_ptr()
-            sd.y, sd.ldy, sd.h_out, sd.tin_out = y.data_ptr(), y.stride(0), h.data_ptr(), tin.data_ptr()
-            keep += [src, row_ids, feats, W1c, W2c, W3c]
-            saved += [ids, feats, h, tin, W2c, W3c]
+            sides[k], y, saved_k, idx, keep_k = _tower_fwd_side(recording, weight, ids, feats, W1, b1, W2, b2, W3, b3)
+            keep.append(keep_k)
+            saved += saved_k
             outs.append(y)
             ctx.lookup_index.append(idx)
             ctx.tower_weight.append(weight)
-        N.check(lib.tt_tower_fwd_pair(sides, B, D, Hd, N.oob.flag(dev).data_ptr(), N.stream()), "tt_tower_fwd_pair")
+        B, D, Hd = outs[1].shape[0], weight.shape[1], W1.shape[0]
+        N.check(N.load().tt_tower_fwd(sides, 2, B, D, Hd, 0, N.oob.flag(dev).data_ptr(), N.stream()), "tt_tower_fwd")
         ctx.save_for_backward(*saved)
         return outs[0], outs[1]
 
@@ -826,32 +848,20 @@ class FusedTowerPair(_LookupFunction):
                 dy = torch.zeros(B, D, dtype=torch.float32, device=dev)
             _resolve_pending(dy)
             dy = dy.contiguous()
-            d_emb = torch.empty(B, D, dtype=torch.float32, device=dev)
-            d_f = torch.empty(B, D, dtype=torch.float32, device=dev)
-            dh = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-            dW1, db1 = torch.empty(Hd, F, dtype=torch.float32, device=dev), torch.empty(Hd, dtype=torch.float32, device=dev)
-            dW2, db2 = torch.empty(D, Hd, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
-            dW3, db3 = torch.empty(D, 2 * D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
-            wsp, wsn = _ws(dev, lib.tt_tower_bwd_weights_workspace_bytes(B, D, F, Hd), "tower_wgrad_pair%d" % k)
-            b = bsides[k]
-            b.dy, b.ldy, b.W2, b.W3, b.h = dy.data_ptr(), dy.stride(0), W2.data_ptr(), W3.data_ptr(), h.data_ptr()
-            b.d_emb, b.ld_demb, b.d_f, b.dh = d_emb.data_ptr(), D, d_f.data_ptr(), dh.data_ptr()
-            w = wsides[k]
-            w.dy, w.ldy, w.tin, w.d_f, w.h, w.dh = dy.data_ptr(), dy.stride(0), tin.data_ptr(), d_f.data_ptr(), h.data_ptr(), dh.data_ptr()
-            w.feats, w.ldf, w.F = feats.data_ptr(), feats.stride(0), F
-            w.dW1, w.db1, w.dW2, w.db2, w.dW3, w.db3 = (x.data_ptr() for x in (dW1, db1, dW2, db2, dW3, db3))
-            w.ws, w.ws_bytes = wsp, wsn
-            keep.append(dy)
-            per.append((ids, d_emb, dW1, db1, dW2, db2, dW3, db3))
-        N.check(lib.tt_tower_bwd_data_pair(bsides, B, D, Hd, N.stream()), "tt_tower_bwd_data_pair")
-        N.check(lib.tt_tower_bwd_weights_pair(wsides, B, D, Hd, N.stream()), "tt_tower_bwd_weights_pair")
-        grads = []
-        for k, (ids, d_emb, dW1, db1, dW2, db2, dW3, db3) in enumerate(per):
+            bsides[k], d_emb, d_f, dh, _ = _tower_bwd_side(dy, h, W2, W3)
+            grads = _tower_grads(dev, D, Hd, F)
+            wsides[k] = _tower_wgrad_side(dy, tin, d_f, h, dh, feats, grads, "tower_wgrad_pair%d" % k)
+            keep.append((dy, d_f, dh))
+            per.append((ids, d_emb, grads))
+        N.check(lib.tt_tower_bwd_data(bsides, 2, B, D, Hd, 0, N.stream()), "tt_tower_bwd_data")
+        N.check(lib.tt_tower_bwd_weights(wsides, 2, B, D, Hd, 0, N.stream()), "tt_tower_bwd_weights")
+        out = []
+        for k, (ids, d_emb, grads) in enumerate(per):
             dweight = None
             if ctx.needs_input_grad[9 * k]:
                 dweight = _route_table_grad(ctx.tower_weight[k], ids.reshape(-1), d_emb, ctx.lookup_index[k])
-            grads += [dweight, None, None, dW1, db1, dW2, db2, dW3, db3]
-        return tuple(grads)
+            out += [dweight, None, None, *grads]
+        return tuple(out)
 
 
 def fused_tower_pair_supported(user_args, item_args) -> bool:
@@ -863,34 +873,22 @@ def fused_tower_pair_supported(user_args, item_args) -> bool:
 
 def tower_weight_grads(dy, tin, d_f, h, dh, feats, out=None, extra=None, side=False):
     """(dW1, db1, dW2, db2, dW3, db3) of one tower: dW3 = dy^T [tin | extra], dW2 = d_f^T h, dW1 = dh^T feats and the
-    bias sums, one product launch + one reduce (tt_tower_bwd_weights_x) instead of three tt_gemm_tn_colsum_f32 calls.
+    bias sums, one product launch + one reduce (tt_tower_bwd_weights) instead of three tt_gemm_tn_colsum_f32 calls.
     `out`: the six tensors to write into (contiguous), else they are allocated.  `extra` [B, 2D]: the third block of
     the tower input (history model), dW3 is then [D, 4D].  `side`: the call is queued on the third stream -- it then uses
     scratch slots of its own (the main stream's products use "ws" / "tower_wgrad" concurrently)."""
     slot_fused, slot_gemm = ("tower_wgrad_side", "ws_side_t") if side else ("tower_wgrad", "ws")
-    dev = dy.device
     B, D = dy.shape
     Hd, F = h.shape[1], feats.shape[1]
     E = 0 if extra is None else extra.shape[1]
-    if out is not None:
-        dW1, db1, dW2, db2, dW3, db3 = out
-    else:
-        dW3 = torch.empty(D, 2 * D + E, dtype=torch.float32, device=dev)
-        dW2 = torch.empty(D, Hd, dtype=torch.float32, device=dev)
-        dW1 = torch.empty(Hd, F, dtype=torch.float32, device=dev)
-        db3 = torch.empty(D, dtype=torch.float32, device=dev)
-        db2 = torch.empty(D, dtype=torch.float32, device=dev)
-        db1 = torch.empty(Hd, dtype=torch.float32, device=dev)
+    dW1, db1, dW2, db2, dW3, db3 = out if out is not None else _tower_grads(dy.device, D, Hd, F, E)
     lib = N.load()
-    if (lib.tt_tower_x_supported(D, F, Hd, D, E) and dy.stride(1) == 1 and dy.stride(0) % 4 == 0 and feats.stride(1) == 1
+    if (lib.tt_tower_supported(D, F, Hd, D, E) and dy.stride(1) == 1 and dy.stride(0) % 4 == 0 and feats.stride(1) == 1
             and all(t.is_contiguous() for t in (tin, d_f, h, dh, dW1, db1, dW2, db2, dW3, db3))
             and all(t.data_ptr() % 16 == 0 for t in (dy, tin, d_f, h, dh))
             and (extra is None or (extra.stride(1) == 1 and extra.stride(0) % 4 == 0 and extra.data_ptr() % 16 == 0))):
-        wsp, wsn = _ws(dev, lib.tt_tower_bwd_weights_x_workspace_bytes(B, D, F, Hd, E), slot_fused)
-        N.check(lib.tt_tower_bwd_weights_x(dy.data_ptr(), dy.stride(0), tin.data_ptr(), d_f.data_ptr(), h.data_ptr(), dh.data_ptr(),
-                                           feats.data_ptr(), feats.stride(0), N.ptr(extra), extra.stride(0) if E else 0, E,
-                                           B, D, F, Hd, dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(),
-                                           dW3.data_ptr(), db3.data_ptr(), wsp, wsn, N.stream()), "tt_tower_bwd_weights_x")
+        sd = _tower_wgrad_side(dy, tin, d_f, h, dh, feats, (dW1, db1, dW2, db2, dW3, db3), slot_fused, extra)
+        N.check(lib.tt_tower_bwd_weights(sd, 1, B, D, Hd, E, N.stream()), "tt_tower_bwd_weights")
         return dW1, db1, dW2, db2, dW3, db3
     if extra is not None:
         gemm_tn_colsum(dy, tin, dW3[:, :2 * D], db=db3, slot=slot_gemm)
