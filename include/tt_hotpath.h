@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define TT_ABI_VERSION 5
+#define TT_ABI_VERSION 6
 
 #define TT_E_BADARG (-1)      /* null pointer / negative size / unsupported shape */
 #define TT_E_WORKSPACE (-2)   /* ws_bytes smaller than tt_*_workspace_bytes()     */
@@ -265,6 +265,34 @@ int tt_inbatch_ce_fwd_du_loss(const float* U, int64_t ldu, const float* I, int64
                               void* ws, int64_t ws_bytes, tt_stream_t stream);
 int tt_scale_rows_g(const float* x, int64_t ldx, const float* coef, const float* g, int64_t rows, int64_t D, float* out,
                     int64_t ldo, float* coef_g, tt_stream_t stream);
+
+/* The in-batch softmax with a per-item additive logit term (log-Q sampling-bias correction, mixed negatives) -- the
+ * correction ref:src/two_tower_base_retrieval.py:289-295 names as missing from the loss of
+ * ref:src/two_tower_base_retrieval.py:287-312.  With b = item_bias [N] (natural-log units, b[j] = -log q_j):
+ *   S'[i,j] = <U[i,:], I[j,:]> + b[j]  for every j, the positive included;  row_ce[i] = logsumexp_j S'[i,j] - S'[i, i+diag_offset]
+ *   G[i,j]  = coef[i] * (softmax_j(S'[i,:]) - [j == i+diag_offset]);  dU = G I,  dI = G^T U;  no gradient flows to b.
+ * The term is one fused multiply-add inside the product kernels (S' is never written either); any D the plain calls take.
+ * item_bias == NULL: exactly the kernels the calls above launch.  `ws`: tt_inbatch_ce_bias_workspace_bytes(M, N, D) (the
+ * plain calls' workspace plus the term's pre-scaled copy; with item_bias == NULL tt_inbatch_ce_workspace_bytes suffices).
+ * tt_inbatch_ce_bias_fwd -- its optional outputs select the form (ref:src/two_tower_base_retrieval.py:287-312, :289-295):
+ *   du_unit == NULL                    tt_inbatch_ce_fwd           (logits and uvw must be NULL too)
+ *   du_unit                            tt_inbatch_ce_fwd_du
+ *   du_unit, logits                    tt_inbatch_ce_fwd_du_keep   (the kept logits INCLUDE the term: tt_inbatch_ce_bwd_kept
+ *                                                                   is the matching item-side backward, unchanged)
+ *   du_unit, uvw (+ labels, T, *_out)  tt_inbatch_ce_fwd_du_loss   (logits and uvw together: TT_E_UNSUPPORTED)
+ * tt_inbatch_ce_bias_bwd -- tt_inbatch_ce_bwd (recomputes S' tile by tile; dU may be NULL) with the same term
+ * (ref:src/two_tower_base_retrieval.py:287-312, :289-295). */
+int64_t tt_inbatch_ce_bias_workspace_bytes(int64_t M, int64_t N, int64_t D);
+int tt_inbatch_ce_bias_fwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                           int64_t diag_offset, const float* item_bias /* [N], may be NULL */, float* row_lse, float* row_ce,
+                           float* du_unit /* may be NULL */, int64_t ld_du, float* logits /* may be NULL */,
+                           int64_t logits_bytes, const float* labels /* may be NULL */, int64_t T,
+                           const float* uvw /* NULL: no loss tail */, float* w_out, float* coef_out, float* loss_out, void* ws,
+                           int64_t ws_bytes, tt_stream_t stream);
+int tt_inbatch_ce_bias_bwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                           int64_t diag_offset, const float* item_bias /* [N], may be NULL */, const float* row_lse,
+                           const float* coef, float* dU /* may be NULL */, int64_t lddu, float* dI, int64_t lddi, void* ws,
+                           int64_t ws_bytes, tt_stream_t stream);
 
 /* Combined debias loss head (ref:src/two_tower_with_debiasing.py:77-129 on top of
  * ref:src/two_tower_base_retrieval.py:322-345), fused -- SURVEY 8f item 2:

@@ -1,4 +1,5 @@
-"""Time the in-batch-softmax CE kernels alone (MI355X).  Usage: python tools/bench_ce.py [M N]"""
+"""Time the in-batch-softmax CE kernels alone (MI355X).  Usage: python tools/bench_ce.py [M N]
+The `*_bias` rows are the same forms with a per-item logit term (log-Q correction: tt_inbatch_ce_bias_fwd / _bwd)."""
 import os
 import sys
 
@@ -53,6 +54,27 @@ for M, Nn in shapes:
         N.check(lib.tt_inbatch_ce_bwd_kept(U.data_ptr(), D, M, Nn, D, 0, lse.data_ptr(), coef.data_ptr(), Z.data_ptr(), zn,
                                            dI2.data_ptr(), D, ws.data_ptr(), wsn, N.stream()), "bwd_kept")
 
+    # the same three forms with a per-item logit term (b = -log q of a Zipf popularity: 2.7 .. 16.5)
+    bias = torch.log(torch.randint(1, 10 ** 6, (Nn,), device=dev).float()) + 2.67
+    wsbn = lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D)
+    wsb = torch.empty(wsbn, dtype=torch.uint8, device=dev)
+    lse_b, ce_b, du_b, dI_b = torch.empty(M, device=dev), torch.empty(M, device=dev), torch.empty(M, D, device=dev), torch.empty(Nn, D, device=dev)
+
+    def fwd_du_bias():
+        N.check(lib.tt_inbatch_ce_bias_fwd(U.data_ptr(), D, I.data_ptr(), D, M, Nn, D, 0, bias.data_ptr(), lse_b.data_ptr(), ce_b.data_ptr(),
+                                           du_b.data_ptr(), D, None, 0, None, 1, None, None, None, None, wsb.data_ptr(), wsbn,
+                                           N.stream()), "fwd_du_bias")
+
+    def bwd_items_bias():
+        N.check(lib.tt_inbatch_ce_bias_bwd(U.data_ptr(), D, I.data_ptr(), D, M, Nn, D, 0, bias.data_ptr(), lse_b.data_ptr(),
+                                           coef.data_ptr(), None, D, dI_b.data_ptr(), D, wsb.data_ptr(), wsbn, N.stream()),
+                "bwd_items_bias")
+
+    def fwd_du_keep_bias():
+        N.check(lib.tt_inbatch_ce_bias_fwd(U.data_ptr(), D, I.data_ptr(), D, M, Nn, D, 0, bias.data_ptr(), lse_b.data_ptr(), ce_b.data_ptr(),
+                                           du_b.data_ptr(), D, Z.data_ptr(), zn, None, 1, None, None, None, None, wsb.data_ptr(), wsbn,
+                                           N.stream()), "fwd_du_keep_bias")
+
     have16 = bool(lib.tt_ce16_supported(M, Nn, D))
     if have16:  # the split-fp16 pair (csrc/ce_f16x2.hip, exploratory)
         ws16n = lib.tt_ce16_workspace_bytes(M, Nn, D)
@@ -93,7 +115,9 @@ for M, Nn in shapes:
 
     for name, fn, flops in ((("fwd", fwd, 2.0 * M * Nn * D), ("bwd", bwd, 8.0 * M * Nn * D),
                              ("fwd_du", fwd_du, 4.0 * M * Nn * D), ("bwd_items", bwd_items, 4.0 * M * Nn * D),
-                             ("fwd_du_keep", fwd_du_keep, 4.0 * M * Nn * D), ("bwd_kept", bwd_kept, 2.0 * M * Nn * D))
+                             ("fwd_du_keep", fwd_du_keep, 4.0 * M * Nn * D), ("bwd_kept", bwd_kept, 2.0 * M * Nn * D),
+                             ("fwd_du_bias", fwd_du_bias, 4.0 * M * Nn * D), ("bwd_items_bias", bwd_items_bias, 4.0 * M * Nn * D),
+                             ("fwd_du_keep_bias", fwd_du_keep_bias, 4.0 * M * Nn * D))
                             + ((("fwd_du_keep_f16x2", fwd_du_keep_f16x2, 4.0 * M * Nn * D),
                                 ("bwd_kept_f16x2", bwd_kept_f16x2, 2.0 * M * Nn * D),
                                 ("fwd_du_nokeep_f16x2", fwd_du_nokeep_f16x2, 4.0 * M * Nn * D),

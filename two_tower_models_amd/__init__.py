@@ -1,6 +1,6 @@
 """MI355X-native hot path of gauravchak/two_tower_models: the reference's nn.Module
 API over hand-written gfx950 HIP kernels (libtt_hotpath.so, C ABI in include/)."""
-from . import parallel
+from . import parallel, sampling
 from .baseline_mips_module import BaselineMIPSModule
 from .graphs import GraphedTrainStep
 from .optim import DenseExactAdam
@@ -16,5 +16,5 @@ __all__ = [
     "BaselineMIPSModule", "DenseExactAdam", "GraphedTrainStep", "TwoTowerBaseRetrieval", "TwoTowerPlusLightRanker",
     "TwoTowerWithDebiasing",
     "TwoTowerWithPositionDebiasedWeights", "TwoTowerWithUserDebiasedWeights", "TwoTowerWithUserHistoryEncoder",
-    "UserHistoryEncoder", "parallel",
+    "UserHistoryEncoder", "parallel", "sampling",
 ]

@@ -23,7 +23,7 @@ TT_COMM_ID_BYTES = 128
 TT_COMM_F32, TT_COMM_I32, TT_COMM_I64, TT_COMM_U8 = 0, 1, 2, 3
 TT_COMM_SUM, TT_COMM_MAX = 0, 1
 TT_MAX_GRAD_SOURCES = 4
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _vp, _i64, _i32, _int = C.c_void_p, C.c_int64, C.c_int32, C.c_int
 
@@ -142,6 +142,11 @@ SIGNATURES = {
     "tt_inbatch_ce_fwd_du_keep": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64,
                                          _vp, _i64, _vp]),
     "tt_inbatch_ce_bwd_kept": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "tt_inbatch_ce_bias_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "tt_inbatch_ce_bias_fwd": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
+                                      _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tt_inbatch_ce_bias_bwd": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                      _i64, _vp]),
     "tt_ce16_supported": (_int, [_i64, _i64, _i64]),
     "tt_ce16_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "tt_ce16_fwd_du_keep": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),

@@ -58,15 +58,83 @@ struct CeArgs {
   float* keep;
   int64_t ldk;
   unsigned* counter;  // fused loss epilogue: arrival counter of the finish kernel's blocks (zeroed by the product kernel)
+  // BIAS kernels: per-ITEM additive logit term, pre-scaled to the log2 domain (b * log2 e), [number of items]
+  const float* bias2;
 };
+
+// ------------------------------------------------------------------ per-item logit term (template flag BIAS)
+// S'[i, j] = <U[i], I[j]> + b[j] (log-Q correction; ref:src/two_tower_base_retrieval.py:289-295 names it as missing).
+// In the log2 domain the corrected logit is ONE fused multiply-add, fma(acc, log2 e, b2[j]), in place of the multiply
+// every form already does: no added VALU instruction per score, and with b2 = 0 it rounds exactly like the multiply.
+// Forward and every backward form the logit with this same single rounded operation (an explicit fma cannot be
+// re-contracted with the backward's `- lse`; contraction is switched off around it all the same).
+__device__ __forceinline__ float fma_rounded(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(a, b, c);
+}
+template <bool BIAS>
+__device__ __forceinline__ float logit2_fwd(float acc, float b2) {
+  if constexpr (BIAS) return fma_rounded(acc, LOG2E, b2);
+  else return acc * LOG2E;
+}
+template <bool BIAS>
+__device__ __forceinline__ float logit2_bwd(float acc, float b2) {  // same rounded s2 as the forward
+  if constexpr (BIAS) return fma_rounded(acc, LOG2E, b2);
+  else return mul_rounded(acc, LOG2E);
+}
+// The lane index formed where it is used, from no input (volatile: not hoisted).  The D = 128 kernels sit at 256 VGPRs
+// (two waves per SIMD); an index or an LDS address derived from threadIdx.x outside the tile loop would live across it
+// in a register they do not have -- two VALU instructions per TILE in one wave instead.
+__device__ __forceinline__ int lane_id_here() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+// Items STREAMED (forward, forward + dU, dU): a tile's 64 terms ride behind the tile in LDS (TILE_FLOATS + BJ), staged
+// with the tile -- by LDS-DMA next to the tile's own (GLDS), else fetched by threads 0..63 at `issue` and written at
+// `land`, the way ce_bwd_kernel<.., STREAM_STATS = true> stages lse / coef -- and are read back as float4 groups right
+// where they are consumed (never 16 values held across a sub-tile).
+template <bool BIAS, bool GLDS>
+struct BiasStage {
+  float v;
+  __device__ __forceinline__ void issue(const float* __restrict__ b2, int64_t row0, int64_t nrows, float* dst, int wave, int lane) {
+    if constexpr (BIAS && GLDS) {
+      // LDS-DMA like the tile itself (one dword per lane of wave 0, 256 B lane-linear; terms past the end are outside
+      // the descriptor's range and land as zeros): no staging register, no ds_write, completes under the tile's vmcnt(0)
+      if (wave == 0) {
+        const int l = lane_id_here();
+        const int64_t left = nrows - row0;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b2 + row0), 0,
+                                                                            (left < BJ ? (int)left : BJ) * 4, 0x00020000);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 4, l * 4, 0, 0, 0);
+      }
+    } else if constexpr (BIAS) {
+      if (threadIdx.x < BJ) {
+        const int64_t b = row0 + threadIdx.x;
+        v = (b < nrows) ? b2[b] : 0.f;
+      }
+    }
+  }
+  __device__ __forceinline__ void land(float* dst) {
+    if constexpr (BIAS && !GLDS) {
+      if (threadIdx.x < BJ) dst[threadIdx.x] = v;
+    }
+  }
+};
+// the four terms of register group q (streamed rows li = jt*32 + 8q + 4h + 0..3); sb = tile + BJ*LD + jt*32 + 4h
+template <bool BIAS>
+__device__ __forceinline__ float4 bias_group(const float* sb, int q) {
+  if constexpr (BIAS) return *reinterpret_cast<const float4*>(sb + 8 * q);
+  else return make_float4(0.f, 0.f, 0.f, 0.f);
+}
 
 // ------------------------------------------------------------------ forward
 // Streams tile t+1 while tile t is on the MFMA pipe.  GLDS: DMA issued at the top of the
 // iteration, drained (vmcnt(0)) right before the barrier that ends it.
-template <int DP8, bool GLDS>
+template <int DP8, bool GLDS, bool BIAS = false>
 __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_kernel(const CeArgs p) {
   using TM = TileMap<DP8, GLDS>;
-  constexpr int TILE_FLOATS = BJ * TM::LD;
+  constexpr int TILE_FLOATS = BJ * TM::LD + (BIAS ? BJ : 0);
   // two NAMED tile buffers, loop unrolled by two (see ce_bwd_kept_kernel)
   __shared__ __attribute__((aligned(16))) float buf0[TILE_FLOATS];
   __shared__ __attribute__((aligned(16))) float buf1[TILE_FLOATS];
@@ -85,13 +153,19 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_kern
   const int64_t want = a + p.diag_offset;
 
   Stager<DP8, GLDS> stg;
-  if (t0 < t1) {
-    stg.issue(p.Y, p.ldy, t0 * BJ, p.RY, p.D, p.y_vec, buf0, wave, lane);
-    stg.land(buf0);
-  }
+  BiasStage<BIAS, GLDS> bst;
+  auto issue = [&](int64_t t, float* dst) {
+    stg.issue(p.Y, p.ldy, t * BJ, p.RY, p.D, p.y_vec, dst, wave, lane);
+    bst.issue(p.bias2, t * BJ, p.RY, dst + BJ * TM::LD, wave, lane);
+  };
+  auto land = [&](float* dst) {
+    bst.land(dst + BJ * TM::LD);
+    stg.land(dst);
+  };
+  if (t0 < t1) { issue(t0, buf0); land(buf0); }
   __syncthreads();
   auto step = [&](int64_t t, const float* ys, float* nxt) {
-    if (t + 1 < t1) stg.issue(p.Y, p.ldy, (t + 1) * BJ, p.RY, p.D, p.y_vec, nxt, wave, lane);
+    if (t + 1 < t1) issue(t + 1, nxt);
     // tile-relative 32-bit indices with the lane term 4h folded in: row (li + 4h) of this tile
     // is the diagonal iff li == want4, and is a real item iff li < lim4
     const int64_t wrel = want - t * BJ, lrel = p.RY - t * BJ;
@@ -102,13 +176,20 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_kern
       const f32x16 acc = score_tile<DP8, GLDS>(ys, xr, jt, r, h);
       float v2[16];
       float tmax = NEG_BIG;
+      const float* sb = ys + BJ * TM::LD + jt * 32 + 4 * h;  // BIAS: this sub-tile's terms
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int li = jt * 32 + (e & 3) + 8 * (e >> 2);  // tile-local row, minus the 4h lane term
-        const float s2 = acc[e] * LOG2E;  // logits are handled in the log2 domain throughout
-        if (li == want4) { dg = s2; has_dg = true; }
-        v2[e] = (li < lim4) ? s2 : NEG_BIG;
-        tmax = fmaxf(tmax, v2[e]);
+      for (int q = 0; q < 4; ++q) {
+        const float4 b4 = bias_group<BIAS>(sb, q);
+        const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int e = 4 * q + c;
+          const int li = jt * 32 + (e & 3) + 8 * (e >> 2);  // tile-local row, minus the 4h lane term
+          const float s2 = logit2_fwd<BIAS>(acc[e], bv[c]);  // logits are handled in the log2 domain throughout
+          if (li == want4) { dg = s2; has_dg = true; }
+          v2[e] = (li < lim4) ? s2 : NEG_BIG;
+          tmax = fmaxf(tmax, v2[e]);
+        }
       }
       const float mn = fmaxf(m, tmax);
       float add = 0.f;
@@ -117,7 +198,7 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_kern
       s = s * fast_exp2(m - mn) + add;
       m = mn;
     }
-    if (t + 1 < t1) stg.land(nxt);
+    if (t + 1 < t1) land(nxt);
     __syncthreads();
   };
   for (int64_t t = t0; t < t1; t += 2) {
@@ -155,11 +236,12 @@ __global__ void ce_fwd_finish_kernel(const float* __restrict__ part_m, const flo
 // ------------------------------------------------------------------ backward
 // STREAM_STATS = false: stationary = users (stats per lane), streamed = items   -> dU
 // STREAM_STATS = true : stationary = items, streamed = users (stats per b)      -> dI
-template <int DP8, bool STREAM_STATS, bool GLDS>
+// BIAS: the per-item term is per STREAMED row for dU (staged behind the tile, BiasStage) and one register per lane for dI.
+template <int DP8, bool STREAM_STATS, bool GLDS, bool BIAS = false>
 __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kernel(const CeArgs p) {
   using TM = TileMap<DP8, GLDS>;
   constexpr int TD = (DP8 + 3) / 4;  // 32-column tiles of the output
-  constexpr int TILE_FLOATS = BJ * TM::LD + (STREAM_STATS ? 2 * BJ : 0);
+  constexpr int TILE_FLOATS = BJ * TM::LD + (STREAM_STATS ? 2 * BJ : (BIAS ? BJ : 0));
   // two NAMED tile buffers (see ce_bwd_kept_kernel): LDS reads of one do not wait for the DMA into the other
   __shared__ __attribute__((aligned(16))) float buf0[TILE_FLOATS];
   __shared__ __attribute__((aligned(16))) float buf1[TILE_FLOATS];
@@ -171,6 +253,8 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
 
   float lse2_a = 0.f, coef_a = 0.f;
   if (!STREAM_STATS && a < p.RX) { lse2_a = p.lse[a]; coef_a = p.coef[a]; }
+  float bias_a = 0.f;  // dI: this lane's item term
+  if constexpr (BIAS && STREAM_STATS) { if (a < p.RX) bias_a = p.bias2[a]; }
 
   const int64_t ntiles_all = (p.RY + BJ - 1) / BJ;
   const int64_t t0 = (int64_t)blockIdx.y * p.tiles_per_split;
@@ -189,20 +273,26 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
     ybase[q] = GLDS ? 4 * h * TM::LD + 4 * ((((r >> 2) ^ (4 * h)) & TM::SW) ^ q) + (r & 3) : 4 * h * TM::LD + r;
 
   Stager<DP8, GLDS> stg;
+  BiasStage<BIAS && !STREAM_STATS, GLDS> bst;
   float st_lse = 0.f, st_coef = 0.f;  // threads 0..63 stage the streamed rows' stats
   auto issue = [&](int64_t t, float* dst) {
     stg.issue(p.Y, p.ldy, t * BJ, p.RY, p.D, p.y_vec, dst, wave, lane);
+    bst.issue(p.bias2, t * BJ, p.RY, dst + BJ * TM::LD, wave, lane);
     if (STREAM_STATS && threadIdx.x < BJ) {
-      const int64_t b = t * BJ + threadIdx.x;
+      // BIAS: the item term took a register of the per-thread row offset kept across the loop (threads 0..63 are wave 0)
+      const int64_t b = t * BJ + ((BIAS && GLDS) ? lane_id_here() : (int)threadIdx.x);
       st_lse = (b < p.RY) ? p.lse[b] : 3.0e38f;
       st_coef = (b < p.RY) ? p.coef[b] : 0.f;
     }
   };
   auto land = [&](float* dst) {
     if (STREAM_STATS && threadIdx.x < BJ) {
-      dst[BJ * TM::LD + threadIdx.x] = st_lse;
-      dst[BJ * TM::LD + BJ + threadIdx.x] = st_coef;
+      // BIAS: the item term took the register that held this address (threads 0..63 are wave 0: lane = thread)
+      const int tid = (BIAS && GLDS) ? lane_id_here() : (int)threadIdx.x;
+      dst[BJ * TM::LD + tid] = st_lse;
+      dst[BJ * TM::LD + BJ + tid] = st_coef;
     }
+    bst.land(dst + BJ * TM::LD);
     stg.land(dst);
   };
 
@@ -223,12 +313,19 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
       const f32x16 acc = score_tile<DP8, GLDS>(ys, xr, jt, r, h);
       float gt[16];
       if constexpr (!STREAM_STATS) {
+        const float* sb = ys + BJ * TM::LD + jt * 32 + 4 * h;  // BIAS: this sub-tile's terms
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int li = jt * 32 + (e & 3) + 8 * (e >> 2);
-          const float pr = fast_exp2(mul_rounded(acc[e], LOG2E) - lse2_a);  // same rounded s2 as the forward
-          const float gval = coef_a * (pr - ((li == want4) ? 1.f : 0.f));
-          gt[e] = (li < lim4) ? gval : 0.f;
+        for (int q = 0; q < 4; ++q) {
+          const float4 b4 = bias_group<BIAS>(sb, q);
+          const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const int e = 4 * q + c;
+            const int li = jt * 32 + (e & 3) + 8 * (e >> 2);
+            const float pr = fast_exp2(logit2_bwd<BIAS>(acc[e], bv[c]) - lse2_a);  // same rounded s2 as the forward
+            const float gval = coef_a * (pr - ((li == want4) ? 1.f : 0.f));
+            gt[e] = (li < lim4) ? gval : 0.f;
+          }
         }
       } else if (no_diag) {  // no diagonal in this tile for any lane of the wave: 4 instead of 7 VALU ops per element
         const float* sl = ys + BJ * TM::LD + jt * 32 + 4 * h;
@@ -237,10 +334,10 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
         for (int q = 0; q < 4; ++q) {
           const float4 l4 = *reinterpret_cast<const float4*>(sl + 8 * q);
           const float4 c4 = *reinterpret_cast<const float4*>(sc + 8 * q);
-          gt[4 * q + 0] = c4.x * fast_exp2(mul_rounded(acc[4 * q + 0], LOG2E) - l4.x);
-          gt[4 * q + 1] = c4.y * fast_exp2(mul_rounded(acc[4 * q + 1], LOG2E) - l4.y);
-          gt[4 * q + 2] = c4.z * fast_exp2(mul_rounded(acc[4 * q + 2], LOG2E) - l4.z);
-          gt[4 * q + 3] = c4.w * fast_exp2(mul_rounded(acc[4 * q + 3], LOG2E) - l4.w);
+          gt[4 * q + 0] = c4.x * fast_exp2(logit2_bwd<BIAS>(acc[4 * q + 0], bias_a) - l4.x);
+          gt[4 * q + 1] = c4.y * fast_exp2(logit2_bwd<BIAS>(acc[4 * q + 1], bias_a) - l4.y);
+          gt[4 * q + 2] = c4.z * fast_exp2(logit2_bwd<BIAS>(acc[4 * q + 2], bias_a) - l4.z);
+          gt[4 * q + 3] = c4.w * fast_exp2(logit2_bwd<BIAS>(acc[4 * q + 3], bias_a) - l4.w);
         }
       } else {
         const float* sl = ys + BJ * TM::LD + jt * 32 + 4 * h;
@@ -254,7 +351,7 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
           for (int c = 0; c < 4; ++c) {
             const int e = 4 * q + c;
             const int li = jt * 32 + (e & 3) + 8 * (e >> 2);
-            const float pr = fast_exp2(mul_rounded(acc[e], LOG2E) - lv[c]);
+            const float pr = fast_exp2(logit2_bwd<BIAS>(acc[e], bias_a) - lv[c]);
             gt[e] = cv[c] * (pr - ((li == want4) ? 1.f : 0.f));  // coef 0 beyond RY
           }
         }
@@ -312,6 +409,7 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
 // brow(e, h) of the sub-tile, exactly the layout the recomputed score tile would have; for a fixed
 // user the 32 lanes of a half-wave read 128 consecutive bytes of its row.  The 32 values of the NEXT
 // tile are requested before this tile's MFMAs and land with the next tile's LDS-DMA.
+// A per-item logit term (BIAS forward) needs NO change here: the kept logits the forward wrote already include it.
 template <int DP8>
 __global__ __launch_bounds__(256, 2) void ce_bwd_kept_kernel(const CeArgs p) {
   using TM = TileMap<DP8, true>;
@@ -476,11 +574,12 @@ __global__ __launch_bounds__(256, 2) void ce_bwd_kept_kernel(const CeArgs p) {
 // cross-half exchange per sub-tile), because their probabilities are summed by the same MFMA.
 // KEEP: the masked log2-domain logits are also written to p.keep (16 B per lane and 4-row group), so
 // the item-side backward (ce_bwd_kept_kernel) reads them back instead of recomputing the product.
-template <int DP8, bool GLDS, bool KEEP = false>
+// BIAS: the per-item terms are read as float4 groups inside the logit loop (the kernel has no 16 registers to spare).
+template <int DP8, bool GLDS, bool KEEP = false, bool BIAS = false>
 __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_du_kernel(const CeArgs p) {
   using TM = TileMap<DP8, GLDS>;
   constexpr int TD = (DP8 + 3) / 4;
-  constexpr int TILE_FLOATS = BJ * TM::LD;
+  constexpr int TILE_FLOATS = BJ * TM::LD + (BIAS ? BJ : 0);
   // two NAMED tile buffers (see ce_bwd_kept_kernel): LDS reads of one no longer wait for the DMA into the other
   __shared__ __attribute__((aligned(16))) float buf0[TILE_FLOATS];
   __shared__ __attribute__((aligned(16))) float buf1[TILE_FLOATS];
@@ -511,13 +610,19 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_du_k
   const int zlane = KEEP ? ((wave * 32 + r) * (int)p.ldk + 4 * h) * 4 : 0;  // byte offset of this lane's logits row
 
   Stager<DP8, GLDS> stg;
-  if (t0 < t1) {
-    stg.issue(p.Y, p.ldy, t0 * BJ, p.RY, p.D, p.y_vec, buf0, wave, lane);
-    stg.land(buf0);
-  }
+  BiasStage<BIAS, GLDS> bst;
+  auto issue = [&](int64_t t, float* dst) {
+    stg.issue(p.Y, p.ldy, t * BJ, p.RY, p.D, p.y_vec, dst, wave, lane);
+    bst.issue(p.bias2, t * BJ, p.RY, dst + BJ * TM::LD, wave, lane);
+  };
+  auto land = [&](float* dst) {
+    bst.land(dst + BJ * TM::LD);
+    stg.land(dst);
+  };
+  if (t0 < t1) { issue(t0, buf0); land(buf0); }
   __syncthreads();
   auto step = [&](int64_t t, const float* ys, float* nxt) {
-    if (t + 1 < t1) stg.issue(p.Y, p.ldy, (t + 1) * BJ, p.RY, p.D, p.y_vec, nxt, wave, lane);
+    if (t + 1 < t1) issue(t + 1, nxt);
     const int64_t wrel = want - t * BJ, lrel = p.RY - t * BJ;
     const int want4 = (wrel >= 0 && wrel < BJ) ? (int)wrel - 4 * h : -1000;
     const int lim4 = (lrel < BJ ? (int)lrel : BJ) - 4 * h;
@@ -535,20 +640,33 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_du_k
       // vmcnt -- the counter the next tile's LDS-DMA completes on
       f32x16 v2 = score_tile<DP8, GLDS>(ys, xr, jt, r, h);
       float tmax = NEG_BIG;
+      const float* sb = ys + BJ * TM::LD + jt * 32 + 4 * h;  // BIAS: this sub-tile's terms
       if (plain) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          v2[e] = v2[e] * LOG2E;
-          tmax = fmaxf(tmax, v2[e]);
+        for (int q = 0; q < 4; ++q) {
+          const float4 b4 = bias_group<BIAS>(sb, q);
+          const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const int e = 4 * q + c;
+            v2[e] = logit2_fwd<BIAS>(v2[e], bv[c]);
+            tmax = fmaxf(tmax, v2[e]);
+          }
         }
       } else {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int li = jt * 32 + (e & 3) + 8 * (e >> 2);
-          const float s2 = v2[e] * LOG2E;
-          if (li == want4) p.diag[a] = s2;  // executes for exactly one (lane, e) per user row
-          v2[e] = (li < lim4) ? s2 : NEG_BIG;
-          tmax = fmaxf(tmax, v2[e]);
+        for (int q = 0; q < 4; ++q) {
+          const float4 b4 = bias_group<BIAS>(sb, q);
+          const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const int e = 4 * q + c;
+            const int li = jt * 32 + (e & 3) + 8 * (e >> 2);
+            const float s2 = logit2_fwd<BIAS>(v2[e], bv[c]);
+            if (li == want4) p.diag[a] = s2;  // executes for exactly one (lane, e) per user row
+            v2[e] = (li < lim4) ? s2 : NEG_BIG;
+            tmax = fmaxf(tmax, v2[e]);
+          }
         }
       }
       if constexpr (KEEP) {  // rows past RX / columns past RY of the padded buffer get 0-logit / NEG_BIG filler
@@ -603,7 +721,7 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_du_k
           dacc[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(v2[e], yv[d], dacc[d], 0, 0, 0);
       }
     }
-    if (t + 1 < t1) stg.land(nxt);
+    if (t + 1 < t1) land(nxt);
     __syncthreads();
   };
   for (int64_t t = t0; t < t1; t += 2) {
@@ -901,7 +1019,7 @@ __global__ __launch_bounds__(256) void scale_rows_g_kernel(const float* __restri
 int64_t ce_wide_workspace_bytes(int64_t M, int64_t N, int64_t D);
 int ce_wide_run(int mode, const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
                 int64_t diag_offset, float* row_lse, float* row_ce, const float* coef, float* dU, int64_t lddu, float* dI,
-                int64_t lddi, void* ws, int64_t ws_bytes, hipStream_t st);
+                int64_t lddi, void* ws, int64_t ws_bytes, hipStream_t st, const float* item_bias = nullptr);
 
 struct CePlan {
   int dp8, splits;
@@ -925,16 +1043,16 @@ static bool plan_ce(int64_t RX, int64_t RY, int64_t D, CePlan& pl) {
 }
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <int DP8, bool GLDS>
+template <int DP8, bool GLDS, bool BIAS>
 static int launch_fwd(const CeArgs& a, dim3 grid, hipStream_t st) {
   ProfScope prof("ce_fwd_kernel", st);
-  ce_fwd_kernel<DP8, GLDS><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
+  ce_fwd_kernel<DP8, GLDS, BIAS><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
   return check_launch("ce_fwd_kernel");
 }
-template <int DP8, bool SS, bool GLDS>
+template <int DP8, bool SS, bool GLDS, bool BIAS>
 static int launch_bwd(const CeArgs& a, dim3 grid, hipStream_t st) {
   ProfScope prof("ce_bwd_kernel", st);
-  ce_bwd_kernel<DP8, SS, GLDS><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
+  ce_bwd_kernel<DP8, SS, GLDS, BIAS><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
   return check_launch("ce_bwd_kernel");
 }
 // LDS-DMA staging needs an unpadded, fully valid row: D == padded D, 16-B aligned rows
@@ -942,14 +1060,19 @@ static bool can_dma(const float* Y, int64_t ld, int64_t D, int dp8) {
   static const bool off = getenv("TT_CE_NO_DMA") != nullptr;
   return !off && D == dp8 * 8 && (ld % 4 == 0) && ld <= (1 << 22) && al16(Y);  // tile_dma: 32-bit byte offsets within a tile
 }
-static int dispatch_fwd(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
-  if (dma) return dp8 == 4 ? launch_fwd<4, true>(a, grid, st) : dp8 == 8 ? launch_fwd<8, true>(a, grid, st) : launch_fwd<16, true>(a, grid, st);
-  return dp8 == 4 ? launch_fwd<4, false>(a, grid, st) : dp8 == 8 ? launch_fwd<8, false>(a, grid, st) : launch_fwd<16, false>(a, grid, st);
+// a.bias2 == nullptr: the BIAS = false instantiations, i.e. exactly the kernels the calls without a term launch
+template <bool BIAS>
+static int dispatch_fwd_b(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
+  if (dma) return dp8 == 4 ? launch_fwd<4, true, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd<8, true, BIAS>(a, grid, st) : launch_fwd<16, true, BIAS>(a, grid, st);
+  return dp8 == 4 ? launch_fwd<4, false, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd<8, false, BIAS>(a, grid, st) : launch_fwd<16, false, BIAS>(a, grid, st);
 }
-template <int DP8, bool GLDS, bool KEEP = false>
+static int dispatch_fwd(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
+  return a.bias2 ? dispatch_fwd_b<true>(dp8, dma, a, grid, st) : dispatch_fwd_b<false>(dp8, dma, a, grid, st);
+}
+template <int DP8, bool GLDS, bool KEEP, bool BIAS>
 static int launch_fwd_du(const CeArgs& a, dim3 grid, hipStream_t st) {
   ProfScope prof("ce_fwd_kernel", st);
-  ce_fwd_du_kernel<DP8, GLDS, KEEP><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
+  ce_fwd_du_kernel<DP8, GLDS, KEEP, BIAS><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
   return check_launch("ce_fwd_du_kernel");
 }
 template <int DP8>
@@ -958,17 +1081,35 @@ static int launch_bwd_kept(const CeArgs& a, dim3 grid, hipStream_t st) {
   ce_bwd_kept_kernel<DP8><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
   return check_launch("ce_bwd_kept_kernel");
 }
-static int dispatch_fwd_du_keep(int dp8, const CeArgs& a, dim3 grid, hipStream_t st) {  // LDS-DMA form only
-  return dp8 == 4 ? launch_fwd_du<4, true, true>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, true, true>(a, grid, st) : launch_fwd_du<16, true, true>(a, grid, st);
+template <bool BIAS>
+static int dispatch_fwd_du_keep_b(int dp8, const CeArgs& a, dim3 grid, hipStream_t st) {  // LDS-DMA form only
+  return dp8 == 4 ? launch_fwd_du<4, true, true, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, true, true, BIAS>(a, grid, st) : launch_fwd_du<16, true, true, BIAS>(a, grid, st);
+}
+static int dispatch_fwd_du_keep(int dp8, const CeArgs& a, dim3 grid, hipStream_t st) {
+  return a.bias2 ? dispatch_fwd_du_keep_b<true>(dp8, a, grid, st) : dispatch_fwd_du_keep_b<false>(dp8, a, grid, st);
+}
+template <bool BIAS>
+static int dispatch_fwd_du_b(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
+  if (dma) return dp8 == 4 ? launch_fwd_du<4, true, false, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, true, false, BIAS>(a, grid, st) : launch_fwd_du<16, true, false, BIAS>(a, grid, st);
+  return dp8 == 4 ? launch_fwd_du<4, false, false, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, false, false, BIAS>(a, grid, st) : launch_fwd_du<16, false, false, BIAS>(a, grid, st);
 }
 static int dispatch_fwd_du(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
-  if (dma) return dp8 == 4 ? launch_fwd_du<4, true>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, true>(a, grid, st) : launch_fwd_du<16, true>(a, grid, st);
-  return dp8 == 4 ? launch_fwd_du<4, false>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, false>(a, grid, st) : launch_fwd_du<16, false>(a, grid, st);
+  return a.bias2 ? dispatch_fwd_du_b<true>(dp8, dma, a, grid, st) : dispatch_fwd_du_b<false>(dp8, dma, a, grid, st);
+}
+template <bool SS, bool BIAS>
+static int dispatch_bwd_b(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
+  if (dma) return dp8 == 4 ? launch_bwd<4, SS, true, BIAS>(a, grid, st) : dp8 == 8 ? launch_bwd<8, SS, true, BIAS>(a, grid, st) : launch_bwd<16, SS, true, BIAS>(a, grid, st);
+  return dp8 == 4 ? launch_bwd<4, SS, false, BIAS>(a, grid, st) : dp8 == 8 ? launch_bwd<8, SS, false, BIAS>(a, grid, st) : launch_bwd<16, SS, false, BIAS>(a, grid, st);
 }
 template <bool SS>
 static int dispatch_bwd(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
-  if (dma) return dp8 == 4 ? launch_bwd<4, SS, true>(a, grid, st) : dp8 == 8 ? launch_bwd<8, SS, true>(a, grid, st) : launch_bwd<16, SS, true>(a, grid, st);
-  return dp8 == 4 ? launch_bwd<4, SS, false>(a, grid, st) : dp8 == 8 ? launch_bwd<8, SS, false>(a, grid, st) : launch_bwd<16, SS, false>(a, grid, st);
+  return a.bias2 ? dispatch_bwd_b<SS, true>(dp8, dma, a, grid, st) : dispatch_bwd_b<SS, false>(dp8, dma, a, grid, st);
+}
+
+// b2[j] = b[j] * log2 e: the per-item term moved to the kernels' log2 domain, once per call
+__global__ __launch_bounds__(256) void ce_bias_scale_kernel(const float* __restrict__ b, int64_t n, float* __restrict__ b2) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < n) b2[j] = mul_rounded(b[j], LOG2E);
 }
 
 }  // namespace tt
@@ -990,14 +1131,15 @@ extern "C" int64_t tt_inbatch_ce_workspace_bytes(int64_t M, int64_t N, int64_t D
   return (most > fwd_du ? most : fwd_du) + 256;  // + the fused loss epilogue's arrival counter (last 256 B)
 }
 
-extern "C" int tt_inbatch_ce_fwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M,
-                                 int64_t N, int64_t D, int64_t diag_offset, float* row_lse, float* row_ce,
-                                 void* ws, int64_t ws_bytes, tt_stream_t stream) {
+// `bias`: the per-item term, natural-log units for D > 128 (ce_wide), pre-scaled to the log2 domain otherwise; may be null
+static int fwd_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                    int64_t diag_offset, float* row_lse, float* row_ce, void* ws, int64_t ws_bytes, tt_stream_t stream,
+                    const float* bias) {
   if (!U || !I || !row_lse || !row_ce || !ws) return fail_arg("tt_inbatch_ce_fwd: null pointer");
   if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D) return fail_arg("tt_inbatch_ce_fwd: sizes");
   if (diag_offset < 0 || diag_offset + M > N) return fail_arg("tt_inbatch_ce_fwd: diagonal outside the item block");
   if (D > 128)
-    return ce_wide_run(0, U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, nullptr, nullptr, 0, nullptr, 0, ws, ws_bytes, S(stream));
+    return ce_wide_run(0, U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, nullptr, nullptr, 0, nullptr, 0, ws, ws_bytes, S(stream), bias);
   CePlan pl;
   if (!plan_ce(M, N, D, pl)) { set_error("tt_inbatch_ce: D=%lld > 128 not implemented", (long long)D); return TT_E_UNSUPPORTED; }
   if (ws_bytes < tt_inbatch_ce_workspace_bytes(M, N, D)) { set_error("tt_inbatch_ce_fwd: workspace"); return TT_E_WORKSPACE; }
@@ -1007,12 +1149,19 @@ extern "C" int tt_inbatch_ce_fwd(const float* U, int64_t ldu, const float* I, in
   a.diag_offset = diag_offset; a.tiles_per_split = pl.tiles_per_split; a.splits = pl.splits;
   a.x_vec = (ldu % 4 == 0) && al16(U); a.y_vec = (ldi % 4 == 0) && al16(I);
   a.part_m = w; a.part_s = w + (int64_t)pl.splits * M; a.diag = w + 2 * (int64_t)pl.splits * M;
+  a.bias2 = bias;
   dim3 grid((unsigned)ceil_div(M, BI), (unsigned)pl.splits);
   hipStream_t st = S(stream);
   int rc = dispatch_fwd(pl.dp8, can_dma(I, ldi, D, pl.dp8), a, grid, st);
   if (rc) return rc;
   ce_fwd_finish_kernel<<<(unsigned)ceil_div(M, 256), 256, 0, st>>>(a.part_m, a.part_s, a.diag, M, pl.splits, row_lse, row_ce);
   return check_launch("ce_fwd_finish_kernel");
+}
+
+extern "C" int tt_inbatch_ce_fwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M,
+                                 int64_t N, int64_t D, int64_t diag_offset, float* row_lse, float* row_ce,
+                                 void* ws, int64_t ws_bytes, tt_stream_t stream) {
+  return fwd_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, ws, ws_bytes, stream, nullptr);
 }
 
 // the kept-logits kernels address a workgroup's 128 rows of the buffer with 32-bit byte offsets
@@ -1030,7 +1179,7 @@ struct CeLossTail {  // the weighted-mean loss head fused behind the forward (tt
 static int fwd_du_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N,
                        int64_t D, int64_t diag_offset, float* row_lse, float* row_ce, float* du_unit,
                        int64_t ld_du, float* logits, int64_t logits_bytes, void* ws, int64_t ws_bytes,
-                       tt_stream_t stream, const CeLossTail* tail = nullptr);
+                       tt_stream_t stream, const CeLossTail* tail = nullptr, const float* bias = nullptr);
 
 extern "C" int tt_inbatch_ce_fwd_du(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N,
                                     int64_t D, int64_t diag_offset, float* row_lse, float* row_ce, float* du_unit,
@@ -1049,14 +1198,14 @@ extern "C" int tt_inbatch_ce_fwd_du_keep(const float* U, int64_t ldu, const floa
 static int fwd_du_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N,
                        int64_t D, int64_t diag_offset, float* row_lse, float* row_ce, float* du_unit,
                        int64_t ld_du, float* logits, int64_t logits_bytes, void* ws, int64_t ws_bytes,
-                       tt_stream_t stream, const CeLossTail* tail) {
+                       tt_stream_t stream, const CeLossTail* tail, const float* bias) {
   if (!U || !I || !row_lse || !row_ce || !du_unit || !ws) return fail_arg("tt_inbatch_ce_fwd_du: null pointer");
   if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D || ld_du < D) return fail_arg("tt_inbatch_ce_fwd_du: sizes");
   if (diag_offset < 0 || diag_offset + M > N) return fail_arg("tt_inbatch_ce_fwd_du: diagonal outside the item block");
   if (D > 128) {
     if (logits) { set_error("tt_inbatch_ce_fwd_du_keep: needs D in {32, 64, 128} (use tt_inbatch_ce_fwd_du)"); return TT_E_UNSUPPORTED; }
     int rc = ce_wide_run(1, U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, nullptr, du_unit, ld_du, nullptr, 0, ws, ws_bytes,
-                         S(stream));
+                         S(stream), bias);
     if (rc || !tail) return rc;
     weighted_mean_loss_kernel<<<1, 1024, 0, S(stream)>>>(tail->labels, M, tail->T, tail->uvw, row_ce, tail->w_out, tail->coef_out,
                                                          tail->loss_out);
@@ -1073,6 +1222,7 @@ static int fwd_du_impl(const float* U, int64_t ldu, const float* I, int64_t ldi,
   a.part_m = w; a.part_s = w + (int64_t)pl.splits * M; a.diag = w + 2 * (int64_t)pl.splits * M;
   a.out = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + round_up((2 * (int64_t)pl.splits * M + M) * 4, 256));
   if (tail) a.counter = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + tt_inbatch_ce_workspace_bytes(M, N, D) - 256);
+  a.bias2 = bias;
   dim3 grid((unsigned)ceil_div(M, BI), (unsigned)pl.splits);
   hipStream_t st = S(stream);
   int rc;
@@ -1121,15 +1271,14 @@ extern "C" int tt_scale_rows_g(const float* x, int64_t ldx, const float* coef, c
   return check_launch("scale_rows_g_kernel");
 }
 
-extern "C" int tt_inbatch_ce_bwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M,
-                                 int64_t N, int64_t D, int64_t diag_offset, const float* row_lse,
-                                 const float* coef, float* dU, int64_t lddu, float* dI, int64_t lddi,
-                                 void* ws, int64_t ws_bytes, tt_stream_t stream) {
+static int bwd_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                    int64_t diag_offset, const float* row_lse, const float* coef, float* dU, int64_t lddu, float* dI,
+                    int64_t lddi, void* ws, int64_t ws_bytes, tt_stream_t stream, const float* bias) {
   if (!U || !I || !row_lse || !coef || !dI || !ws) return fail_arg("tt_inbatch_ce_bwd: null pointer");
   if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D || (dU && lddu < D) || lddi < D) return fail_arg("tt_inbatch_ce_bwd: sizes");
   if (D > 128)
     return ce_wide_run(2, U, ldu, I, ldi, M, N, D, diag_offset, const_cast<float*>(row_lse), nullptr, coef, dU, lddu, dI, lddi, ws,
-                       ws_bytes, S(stream));
+                       ws_bytes, S(stream), bias);
   CePlan pu, pi;
   if (!plan_ce(M, N, D, pu) || !plan_ce(N, M, D, pi)) { set_error("tt_inbatch_ce: D=%lld > 128 not implemented", (long long)D); return TT_E_UNSUPPORTED; }
   if (ws_bytes < tt_inbatch_ce_workspace_bytes(M, N, D)) { set_error("tt_inbatch_ce_bwd: workspace"); return TT_E_WORKSPACE; }
@@ -1143,7 +1292,7 @@ extern "C" int tt_inbatch_ce_bwd(const float* U, int64_t ldu, const float* I, in
     a.X = U; a.Y = I; a.ldx = ldu; a.ldy = ldi; a.RX = M; a.RY = N; a.D = D; a.diag_offset = diag_offset;
     a.tiles_per_split = pu.tiles_per_split; a.splits = pu.splits;
     a.x_vec = (ldu % 4 == 0) && al16(U); a.y_vec = (ldi % 4 == 0) && al16(I);
-    a.lse = row_lse; a.coef = coef; a.out = pu.splits > 1 ? slab_u : dU; a.ldo = lddu;
+    a.lse = row_lse; a.coef = coef; a.out = pu.splits > 1 ? slab_u : dU; a.ldo = lddu; a.bias2 = bias;
     dim3 grid((unsigned)ceil_div(M, BI), (unsigned)pu.splits);
     rc = dispatch_bwd<false>(pu.dp8, can_dma(I, ldi, D, pu.dp8), a, grid, st);
     if (rc) return rc;
@@ -1156,7 +1305,7 @@ extern "C" int tt_inbatch_ce_bwd(const float* U, int64_t ldu, const float* I, in
     a.X = I; a.Y = U; a.ldx = ldi; a.ldy = ldu; a.RX = N; a.RY = M; a.D = D; a.diag_offset = diag_offset;
     a.tiles_per_split = pi.tiles_per_split; a.splits = pi.splits;
     a.x_vec = (ldi % 4 == 0) && al16(I); a.y_vec = (ldu % 4 == 0) && al16(U);
-    a.lse = row_lse; a.coef = coef; a.out = pi.splits > 1 ? slab_i : dI; a.ldo = lddi;
+    a.lse = row_lse; a.coef = coef; a.out = pi.splits > 1 ? slab_i : dI; a.ldo = lddi; a.bias2 = bias;
     dim3 grid((unsigned)ceil_div(N, BI), (unsigned)pi.splits);
     rc = dispatch_bwd<true>(pi.dp8, can_dma(U, ldu, D, pi.dp8), a, grid, st);
     if (rc) return rc;
@@ -1165,6 +1314,67 @@ extern "C" int tt_inbatch_ce_bwd(const float* U, int64_t ldu, const float* I, in
     }
   }
   return 0;
+}
+
+extern "C" int tt_inbatch_ce_bwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M,
+                                 int64_t N, int64_t D, int64_t diag_offset, const float* row_lse,
+                                 const float* coef, float* dU, int64_t lddu, float* dI, int64_t lddi,
+                                 void* ws, int64_t ws_bytes, tt_stream_t stream) {
+  return bwd_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, coef, dU, lddu, dI, lddi, ws, ws_bytes, stream, nullptr);
+}
+
+// ------------------------------------------------------------------ the same calls with a per-item logit term
+extern "C" int64_t tt_inbatch_ce_bias_workspace_bytes(int64_t M, int64_t N, int64_t D) {
+  const int64_t base = tt_inbatch_ce_workspace_bytes(M, N, D);
+  return base > 0 ? base + round_up(N * 4, 256) : 0;  // + the pre-scaled copy of the term, behind the plain calls' workspace
+}
+
+// the pre-scaled copy (D <= 128; ce_wide works in natural-log units and takes the term as it is); null term: null
+static const float* stage_bias(const float* item_bias, int64_t M, int64_t N, int64_t D, void* ws, hipStream_t st, int* rc) {
+  *rc = 0;
+  if (!item_bias || D > 128) return item_bias;
+  float* b2 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + tt_inbatch_ce_workspace_bytes(M, N, D));
+  ce_bias_scale_kernel<<<(unsigned)ceil_div(N, 256), 256, 0, st>>>(item_bias, N, b2);
+  *rc = check_launch("ce_bias_scale_kernel");
+  return b2;
+}
+
+extern "C" int tt_inbatch_ce_bias_fwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                                      int64_t diag_offset, const float* item_bias, float* row_lse, float* row_ce,
+                                      float* du_unit, int64_t ld_du, float* logits, int64_t logits_bytes, const float* labels,
+                                      int64_t T, const float* uvw, float* w_out, float* coef_out, float* loss_out, void* ws,
+                                      int64_t ws_bytes, tt_stream_t stream) {
+  if (!U || !I || !row_lse || !row_ce || !ws) return fail_arg("tt_inbatch_ce_bias_fwd: null pointer");
+  if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D || (du_unit && ld_du < D)) return fail_arg("tt_inbatch_ce_bias_fwd: sizes");
+  if (diag_offset < 0 || diag_offset + M > N) return fail_arg("tt_inbatch_ce_bias_fwd: diagonal outside the item block");
+  if (!du_unit && (logits || uvw)) return fail_arg("tt_inbatch_ce_bias_fwd: kept logits and the loss tail need du_unit");
+  if (uvw && (!w_out || !coef_out || !loss_out)) return fail_arg("tt_inbatch_ce_bias_fwd: null pointer");
+  if (uvw && labels && T <= 0) return fail_arg("tt_inbatch_ce_bias_fwd: sizes");
+  if (logits && uvw) { set_error("tt_inbatch_ce_bias_fwd: kept logits and the fused loss tail together"); return TT_E_UNSUPPORTED; }
+  const int64_t need = item_bias ? tt_inbatch_ce_bias_workspace_bytes(M, N, D) : tt_inbatch_ce_workspace_bytes(M, N, D);
+  if (ws_bytes < need) { set_error("tt_inbatch_ce_bias_fwd: workspace"); return TT_E_WORKSPACE; }
+  int rc;
+  const float* bias = stage_bias(item_bias, M, N, D, ws, S(stream), &rc);
+  if (rc) return rc;
+  if (!du_unit) return fwd_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, ws, ws_bytes, stream, bias);
+  const CeLossTail tail{labels, T, uvw, w_out, coef_out, loss_out};
+  return fwd_du_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, du_unit, ld_du, logits, logits_bytes, ws, ws_bytes,
+                     stream, uvw ? &tail : nullptr, bias);
+}
+
+extern "C" int tt_inbatch_ce_bias_bwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                                      int64_t diag_offset, const float* item_bias, const float* row_lse, const float* coef,
+                                      float* dU, int64_t lddu, float* dI, int64_t lddi, void* ws, int64_t ws_bytes,
+                                      tt_stream_t stream) {
+  if (!U || !I || !row_lse || !coef || !dI || !ws) return fail_arg("tt_inbatch_ce_bias_bwd: null pointer");
+  if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D || (dU && lddu < D) || lddi < D) return fail_arg("tt_inbatch_ce_bias_bwd: sizes");
+  if (diag_offset < 0 || diag_offset + M > N) return fail_arg("tt_inbatch_ce_bias_bwd: diagonal outside the item block");
+  const int64_t need = item_bias ? tt_inbatch_ce_bias_workspace_bytes(M, N, D) : tt_inbatch_ce_workspace_bytes(M, N, D);
+  if (ws_bytes < need) { set_error("tt_inbatch_ce_bias_bwd: workspace"); return TT_E_WORKSPACE; }
+  int rc;
+  const float* bias = stage_bias(item_bias, M, N, D, ws, S(stream), &rc);
+  if (rc) return rc;
+  return bwd_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, coef, dU, lddu, dI, lddi, ws, ws_bytes, stream, bias);
 }
 
 extern "C" int tt_inbatch_ce_bwd_kept(const float* U, int64_t ldu, int64_t M, int64_t N, int64_t D, int64_t diag_offset,

@@ -924,21 +924,41 @@ def _release_held_sweeps(before_kernel: Optional[torch.cuda.Event]) -> None:
         opt.release_sweep(after=before_kernel)
 
 
+def _item_bias(item_bias: Optional[torch.Tensor], I: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+    """The per-item additive logit term b[j] (= -log q_j, natural-log units): float32 [N] on the items' device."""
+    if item_bias is None:
+        return None
+    if not isinstance(item_bias, torch.Tensor) or item_bias.dtype != torch.float32:
+        raise TypeError(f"{what}: item_bias must be a float32 tensor, got {getattr(item_bias, 'dtype', type(item_bias))}")
+    if item_bias.device != I.device:
+        raise RuntimeError(f"{what}: item_bias is on {item_bias.device}, the item embeddings on {I.device}")
+    if item_bias.dim() != 1 or item_bias.shape[0] != I.shape[0]:
+        raise ValueError(f"{what}: item_bias must have one value per item row, [{I.shape[0]}]; got {tuple(item_bias.shape)}")
+    return item_bias.detach().contiguous()  # no gradient flows to the term
+
+
 class InBatchSoftmaxCE(torch.autograd.Function):
-    """row_ce[i] = logsumexp_j (U I^T)[i, j] - (U I^T)[i, i + diag_offset]
-    (torch.matmul + F.cross_entropy(reduction="none"), ref:...base_retrieval.py:287-312)."""
+    """row_ce[i] = logsumexp_j S'[i, j] - S'[i, i + diag_offset],  S' = U I^T (+ item_bias[None, :])
+    (torch.matmul + F.cross_entropy(reduction="none"), ref:...base_retrieval.py:287-312; the per-item term is the
+    log-Q correction ref:...base_retrieval.py:289-295 names as missing)."""
 
     @staticmethod
-    def forward(ctx, U, I, diag_offset: int = 0, keep_logits: Optional[bool] = None):
+    def forward(ctx, U, I, diag_offset: int = 0, keep_logits: Optional[bool] = None, item_bias: Optional[torch.Tensor] = None):
         """`keep_logits`: write the [M, N] logits out in the forward so the item-side backward does not
         recompute them (3 instead of 4 logit-sized products, for M*N*4 B of HBM each way).  Default:
         only for wide negative sets (N >= 4 M, i.e. several ranks' items per user) -- at N = M the
-        step is bound by the Adam sweep's HBM traffic and the extra bytes cost more than the MFMAs."""
+        step is bound by the Adam sweep's HBM traffic and the extra bytes cost more than the MFMAs.
+        `item_bias`: float32 [N], added to every logit of its column (the positive included) inside the product
+        kernels; receives no gradient.  With it the fp32-MFMA kernels run (never the exploratory split-fp16 pair)."""
         dev = N.require_device(U, I)
         U, I = _rowmajor(U), _rowmajor(I)
         M, D = U.shape
         Nn = I.shape[0]
         lib = N.load()
+        item_bias = _item_bias(item_bias, I, "InBatchSoftmaxCE")
+        if item_bias is not None:
+            return InBatchSoftmaxCE._forward_biased(ctx, lib, dev, U, I, M, Nn, D, diag_offset, keep_logits, item_bias)
+        ctx.biased = False
         lse = torch.empty(M, dtype=torch.float32, device=dev)
         ce = torch.empty(M, dtype=torch.float32, device=dev)
         wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
@@ -988,9 +1008,48 @@ class InBatchSoftmaxCE(torch.autograd.Function):
         return ce
 
     @staticmethod
+    def _forward_biased(ctx, lib, dev, U, I, M, Nn, D, diag_offset, keep_logits, item_bias):
+        """The same three forms (plain / + du_unit / + kept logits) through tt_inbatch_ce_bias_fwd."""
+        ctx.biased = True
+        ctx.diag_offset = diag_offset
+        ctx.kept = ctx.kept16 = None
+        lse = torch.empty(M, dtype=torch.float32, device=dev)
+        ce = torch.empty(M, dtype=torch.float32, device=dev)
+        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
+        pu, _, _, ldu = _f32_2d(U, "U")
+        pi, _, _, ldi = _f32_2d(I, "I")
+        du_unit, zp, zn = None, None, 0
+        if ctx.needs_input_grad[0]:
+            du_unit = torch.empty(M, D, dtype=torch.float32, device=dev)
+            if D > 128:
+                note_generic("in-batch softmax CE", f"D = {D} > 128: logits materialised per row chunk + library GEMMs "
+                                                    "(csrc/ce_wide.hip) instead of the register-stationary kernels")
+            if keep_logits is None:
+                keep_logits = Nn >= 4 * M
+            if keep_logits and ctx.needs_input_grad[1] and not kept_logits_supported(U, I):
+                note_generic("in-batch softmax CE backward (wide negative sets)",
+                             f"kept logits need D in {{32, 64, 128}}, N < 4 Mi and 16-B aligned rows; got D = {D}, N = {Nn}: "
+                             "the item-side backward recomputes the logits (4 instead of 3 logit-sized products)")
+            if bool(keep_logits) and ctx.needs_input_grad[1] and kept_logits_supported(U, I):
+                zn = lib.tt_inbatch_ce_logits_bytes(M, Nn)
+                ctx.kept = torch.empty(zn, dtype=torch.uint8, device=dev)
+                zp = ctx.kept.data_ptr()
+        N.check(lib.tt_inbatch_ce_bias_fwd(pu, ldu, pi, ldi, M, Nn, D, diag_offset, item_bias.data_ptr(), lse.data_ptr(), ce.data_ptr(),
+                                           N.ptr(du_unit), D, zp, zn, None, 0, None, None, None, None, wsp, wsn, N.stream()),
+                "tt_inbatch_ce_bias_fwd")
+        if du_unit is not None:
+            ctx.save_for_backward(U, I, lse, item_bias, du_unit)
+        else:
+            ctx.save_for_backward(U, I, lse, item_bias)
+        return ce
+
+    @staticmethod
     def backward(ctx, d_ce):
         saved = ctx.saved_tensors
         U, I, lse = saved[:3]
+        item_bias = None
+        if ctx.biased:
+            item_bias, saved = saved[3], saved[:3] + saved[4:]
         du_unit = saved[3] if len(saved) > 3 else None
         dev = U.device
         M, D = U.shape
@@ -1001,7 +1060,8 @@ class InBatchSoftmaxCE(torch.autograd.Function):
         if du_unit is not None:
             N.check(lib.tt_scale_rows(du_unit.data_ptr(), D, coef.data_ptr(), M, D, dU.data_ptr(), D, N.stream()), "tt_scale_rows")
         dI = torch.empty(Nn, D, dtype=torch.float32, device=dev)
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
+        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D) if item_bias is None
+                       else lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
         pu, _, _, ldu = _f32_2d(U, "U")
         pi, _, _, ldi = _f32_2d(I, "I")
         before = None
@@ -1009,13 +1069,14 @@ class InBatchSoftmaxCE(torch.autograd.Function):
             before = torch.cuda.Event()
             before.record()
         try:
-            return InBatchSoftmaxCE._item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn)
+            return InBatchSoftmaxCE._item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn,
+                                               item_bias)
         finally:
             if before is not None:
                 _release_held_sweeps(before)
 
     @staticmethod
-    def _item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn):
+    def _item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn, item_bias=None):
         if ctx.kept16 is not None:  # the split-fp16 pair's backward
             w16p, w16n = _ws(dev, lib.tt_ce16_workspace_bytes(M, Nn, D), "ce16")
             if ctx.kept16 is True:  # (images formed again: other products may have used the workspace slot since the forward)
@@ -1025,17 +1086,22 @@ class InBatchSoftmaxCE(torch.autograd.Function):
                 N.check(lib.tt_ce16_bwd_kept(pu, D, M, Nn, D, ctx.diag_offset, lse.data_ptr(), coef.data_ptr(), ctx.kept16.data_ptr(),
                                              M * Nn * 4, dI.data_ptr(), D, w16p, w16n, N.stream()), "tt_ce16_bwd_kept")
             ctx.kept16 = None
-            return dU, dI, None, None
-        if ctx.kept is not None:  # item side from the logits the forward kept
+            return dU, dI, None, None, None
+        if ctx.kept is not None:  # item side from the logits the forward kept (they include the per-item term, if any)
             N.check(lib.tt_inbatch_ce_bwd_kept(pu, ldu, M, Nn, D, ctx.diag_offset, lse.data_ptr(), coef.data_ptr(),
                                                ctx.kept.data_ptr(), ctx.kept.numel(), dI.data_ptr(), D, wsp, wsn,
                                                N.stream()), "tt_inbatch_ce_bwd_kept")
             ctx.kept = None
-            return dU, dI, None, None
+            return dU, dI, None, None, None
+        if item_bias is not None:
+            N.check(lib.tt_inbatch_ce_bias_bwd(pu, ldu, pi, ldi, M, Nn, D, ctx.diag_offset, item_bias.data_ptr(), lse.data_ptr(),
+                                               coef.data_ptr(), None if du_unit is not None else dU.data_ptr(), D,
+                                               dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bias_bwd")
+            return dU, dI, None, None, None
         N.check(lib.tt_inbatch_ce_bwd(pu, ldu, pi, ldi, M, Nn, D, ctx.diag_offset, lse.data_ptr(),
                                       coef.data_ptr(), None if du_unit is not None else dU.data_ptr(), D,
                                       dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bwd")
-        return dU, dI, None, None
+        return dU, dI, None, None, None
 
 
 def _labels_f32(labels: torch.Tensor, what: str) -> torch.Tensor:
@@ -1097,11 +1163,12 @@ def ce16_usable(U: torch.Tensor, I: torch.Tensor) -> bool:
                 and N.load().tt_ce16_supported(U.shape[0], I.shape[0], U.shape[1]))
 
 
-def fused_loss_supported(U: torch.Tensor, I: torch.Tensor, labels: Optional[torch.Tensor], uvw: torch.Tensor) -> bool:
+def fused_loss_supported(U: torch.Tensor, I: torch.Tensor, labels: Optional[torch.Tensor], uvw: torch.Tensor,
+                         item_bias: Optional[torch.Tensor] = None) -> bool:
     """InBatchSoftmaxWeightedLoss: a training forward (U needs a gradient) with in-batch negatives only (N < 4 M: the wide
     form keeps its logits and has its own forward), float32 everywhere, one label row per user row."""
-    if ce16_usable(U, I):
-        return False  # the split-fp16 pair is a two-op path: InBatchSoftmaxCE + WeightedMeanLoss
+    if item_bias is None and ce16_usable(U, I):
+        return False  # the split-fp16 pair is a two-op path: InBatchSoftmaxCE + WeightedMeanLoss (never taken with a bias)
     return bool(U.is_cuda and U.requires_grad and torch.is_grad_enabled() and U.dim() == 2 and I.dim() == 2
                 and U.dtype == torch.float32 and I.dtype == torch.float32 and uvw.dtype == torch.float32
                 and I.shape[0] < 4 * U.shape[0]
@@ -1113,14 +1180,17 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
     """WeightedMeanLoss(InBatchSoftmaxCE(U, I), labels, uvw) as one op: the loss head runs in the launch that finishes
     the forward (tt_inbatch_ce_fwd_du_loss; ref:src/two_tower_base_retrieval.py:287-312,322,334-343), and the backward
     starts with ONE launch that forms dL/dce * g and dU (tt_scale_rows_g) instead of an elementwise multiply and a row
-    scaling.  Same values as the two ops, bit for bit; two launches fewer on the step's critical path."""
+    scaling.  Same values as the two ops, bit for bit; two launches fewer on the step's critical path.
+    `item_bias` (float32 [N], optional): the per-item logit term of InBatchSoftmaxCE; no gradient."""
 
     @staticmethod
-    def forward(ctx, U, I, labels, uvw):
+    def forward(ctx, U, I, labels, uvw, item_bias: Optional[torch.Tensor] = None):
         dev = N.require_device(U, I, labels, uvw)
         U, I, uvw = _rowmajor(U), _rowmajor(I), uvw.contiguous()
         M, D = U.shape
         Nn = I.shape[0]
+        item_bias = _item_bias(item_bias, I, "InBatchSoftmaxWeightedLoss")
+        ctx.biased = item_bias is not None
         T = 1
         if labels is not None:
             labels = _labels_f32(labels, "InBatchSoftmaxWeightedLoss")
@@ -1135,9 +1205,16 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
         coef = torch.empty(M, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         du_unit = torch.empty(M, D, dtype=torch.float32, device=dev)
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
         pu, _, _, ldu = _f32_2d(U, "U")
         pi, _, _, ldi = _f32_2d(I, "I")
+        if item_bias is not None:
+            wsp, wsn = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
+            N.check(lib.tt_inbatch_ce_bias_fwd(pu, ldu, pi, ldi, M, Nn, D, 0, item_bias.data_ptr(), lse.data_ptr(), ce.data_ptr(),
+                                               du_unit.data_ptr(), D, None, 0, N.ptr(labels), T, uvw.data_ptr(), w.data_ptr(),
+                                               coef.data_ptr(), loss.data_ptr(), wsp, wsn, N.stream()), "tt_inbatch_ce_bias_fwd")
+            ctx.save_for_backward(U, I, lse, du_unit, coef, item_bias)
+            return loss
+        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
         N.check(lib.tt_inbatch_ce_fwd_du_loss(pu, ldu, pi, ldi, M, Nn, D, 0, N.ptr(labels), T, uvw.data_ptr(), lse.data_ptr(),
                                               ce.data_ptr(), du_unit.data_ptr(), D, w.data_ptr(), coef.data_ptr(), loss.data_ptr(),
                                               wsp, wsn, N.stream()), "tt_inbatch_ce_fwd_du_loss")
@@ -1146,7 +1223,8 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        U, I, lse, du_unit, coef = ctx.saved_tensors
+        U, I, lse, du_unit, coef = ctx.saved_tensors[:5]
+        item_bias = ctx.saved_tensors[5] if ctx.biased else None
         dev = U.device
         M, D = U.shape
         Nn = I.shape[0]
@@ -1157,12 +1235,17 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
         N.check(lib.tt_scale_rows_g(du_unit.data_ptr(), D, coef.data_ptr(), g.data_ptr(), M, D, dU.data_ptr(), D, coef_g.data_ptr(),
                                     N.stream()), "tt_scale_rows_g")
         dI = torch.empty(Nn, D, dtype=torch.float32, device=dev)
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
         pu, _, _, ldu = _f32_2d(U, "U")
         pi, _, _, ldi = _f32_2d(I, "I")
+        if item_bias is not None:
+            wsp, wsn = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
+            N.check(lib.tt_inbatch_ce_bias_bwd(pu, ldu, pi, ldi, M, Nn, D, 0, item_bias.data_ptr(), lse.data_ptr(), coef_g.data_ptr(),
+                                               None, D, dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bias_bwd")
+            return dU, dI, None, None, None
+        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
         N.check(lib.tt_inbatch_ce_bwd(pu, ldu, pi, ldi, M, Nn, D, 0, lse.data_ptr(), coef_g.data_ptr(), None, D,
                                       dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bwd")
-        return dU, dI, None, None
+        return dU, dI, None, None, None
 
 
 class DebiasedWeightedLoss(torch.autograd.Function):

@@ -30,7 +30,7 @@ from typing import Optional
 import torch
 
 from . import BaselineMIPSModule, DenseExactAdam, TwoTowerBaseRetrieval, TwoTowerWithDebiasing, \
-    TwoTowerWithUserHistoryEncoder, parallel
+    TwoTowerWithUserHistoryEncoder, parallel, sampling
 
 
 class DummyRecDataset:
@@ -85,11 +85,40 @@ class DeviceBatches:
             yield tuple(f[idx] for f in self.dataset.fields())
 
 
-def train_one_epoch(model, dataloader, optimizer, device):
+class CandidateSampler:
+    """What ``--logq`` / ``--num_random_negatives`` add to a batch, drawn on the device: the log sampling probability of
+    the batch's own items (unigram table of the data set's item ids, built once) and, per step, Bn uniform item ids with
+    ``randn`` features from a seeded generator.  With both, log q is the mixture form (sampling.mixture_log_q)."""
+
+    def __init__(self, dataset: DummyRecDataset, logq: bool, num_random_negatives: int, seed: int = 4321):
+        dev = dataset.item_ids.device
+        self.num_items, self.feature_dim, self.n_neg = dataset.num_items, dataset.feature_dim, int(num_random_negatives)
+        self.gen = torch.Generator(device=dev).manual_seed(seed)
+        self.log_p = None
+        if logq:
+            self.log_p = sampling.log_q_from_counts(torch.bincount(dataset.item_ids, minlength=dataset.num_items))
+
+    def __call__(self, item_ids: torch.Tensor) -> dict:
+        """Keywords for ``train_forward`` for the batch whose items are ``item_ids``."""
+        kw, B, dev = {}, item_ids.shape[0], item_ids.device
+        neg = None
+        if self.n_neg > 0:
+            neg = torch.randint(0, self.num_items, (self.n_neg,), device=dev, generator=self.gen)
+            kw["negative_item_id"] = neg
+            kw["negative_item_features"] = torch.randn(self.n_neg, self.feature_dim, device=dev, generator=self.gen)
+        if self.log_p is not None:
+            kw["item_log_q"] = sampling.mixture_log_q(self.log_p, item_ids, B, self.n_neg, self.num_items)
+            if neg is not None:
+                kw["negative_log_q"] = sampling.mixture_log_q(self.log_p, neg, B, self.n_neg, self.num_items)
+        return kw
+
+
+def train_one_epoch(model, dataloader, optimizer, device, candidates=None):
     """ref:train/train.py:85-135: forward -> zero_grad -> backward -> step per batch; returns
     the mean loss.  The per-step ``.item()`` of upstream is replaced by one at the end.
     Row-sharded model: the NEXT batch's lookups are announced underneath the current step (parallel.plan_ahead), which
-    is what lets the host run ahead of the GPU; purely a scheduling hint."""
+    is what lets the host run ahead of the GPU; purely a scheduling hint.
+    ``candidates`` (a CandidateSampler; default None = the reference's loop): log-Q terms / extra negatives per batch."""
     model.train()
     total_loss = None
     sharded = parallel.is_sharded(model)
@@ -97,8 +126,9 @@ def train_one_epoch(model, dataloader, optimizer, device):
     batch = next(batches, None)
     while batch is not None:
         user_ids, user_features, user_history, item_ids, item_features, positions, labels = (t.to(device) for t in batch)
+        extra = candidates(item_ids) if candidates is not None else {}
         batch_loss = model.train_forward(user_ids, user_features, user_history, item_ids, item_features,
-                                         positions, labels)
+                                         positions, labels, **extra)
         batch = next(batches, None)
         if sharded and batch is not None:
             parallel.plan_ahead(model._lookup_plan(batch[0], batch[2], batch[3]))
@@ -138,6 +168,11 @@ def main(args):
         raise SystemExit("two_tower_models_amd.train needs an MI355X (ROCm) device; there is no CPU path")
     world = int(getattr(args, "world_size", 0) or os.environ.get("WORLD_SIZE", "1"))
     rank = 0
+    logq, n_neg = bool(getattr(args, "logq", False)), int(getattr(args, "num_random_negatives", 0) or 0)
+    if n_neg < 0:
+        raise SystemExit("--num_random_negatives must be >= 0")
+    if world > 1 and (logq or n_neg):
+        raise SystemExit("--logq / --num_random_negatives are not implemented with --world_size > 1 (row-sharded tables)")
     if world > 1:
         device, rank = _init_distributed(world)
     else:
@@ -168,11 +203,15 @@ def main(args):
     # forward-announced sweep start assumes (optim.py)
     optimizer = DenseExactAdam(model.parameters(), lr=args.learning_rate, overlap_sweep="forward",
                                lazy=getattr(args, "lazy_adam", False))
+    candidates = CandidateSampler(dataset, logq, n_neg) if (logq or n_neg) else None
     stats = []
     for epoch in range(args.num_epochs):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        avg_loss = train_one_epoch(model, dataloader, optimizer, device)  # ends with .item(): the device has drained
+        if candidates is None:
+            avg_loss = train_one_epoch(model, dataloader, optimizer, device)  # ends with .item(): the device has drained
+        else:
+            avg_loss = train_one_epoch(model, dataloader, optimizer, device, candidates=candidates)
         dt = time.perf_counter() - t0
         say(f"Epoch [{epoch + 1}/{args.num_epochs}] - Loss: {avg_loss:.4f}")
         stats.append({"epoch": epoch + 1, "loss": avg_loss, "seconds": dt, "pairs_per_s": len(dataset) * world / dt})
@@ -233,6 +272,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--retrieve", action="store_true",
                    help="after training: index the catalogue with the trained item tower (model.index_corpus; item r = row r of "
                         "the item table, random features) and run model.forward() on one batch -- row-sharded with --world_size N")
+    p.add_argument("--logq", action="store_true",
+                   help="log-Q sampling-bias correction of the in-batch softmax: subtract log q_j (unigram table of the data "
+                        "set's item ids; with --num_random_negatives the unigram / uniform mixture) from every logit column")
+    p.add_argument("--num_random_negatives", type=int, default=0,
+                   help="mixed negative sampling: this many uniformly drawn items (random features) per step next to the "
+                        "in-batch negatives")
     p.add_argument("--lazy_adam", action="store_true",
                    help="value-exact deferred Adam: replay a row's zero-gradient steps when it is next needed")
     return p

@@ -16,7 +16,7 @@ below stays overridable.
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -207,11 +207,20 @@ class TwoTowerBaseRetrieval(nn.Module):
         item_embeddings: torch.Tensor,  # [B, DI]
         position: torch.Tensor,  # [B]
         labels: torch.Tensor,  # [B, T]
+        item_log_q: Optional[torch.Tensor] = None,  # [N], N = item_embeddings.shape[0] >= B
     ) -> torch.Tensor:
         """In-batch softmax loss weighted by normalised net user value (ref :279-347).
-        The [B, B] logits are never materialised."""
+        The [B, B] logits are never materialised.
+
+        ``item_log_q`` (float32, one value per item row): log of the probability with which each candidate was drawn.
+        The logits become ``<u_i, v_j> - item_log_q[j]`` for every column, the positive included -- the log-Q
+        sampling-bias correction ref :289-295 names as missing (Yi et al. 2019, eq. 3).  ``item_embeddings`` may carry
+        extra rows behind the batch's own B (mixed negatives): the positive of user i stays item row i."""
         if self._sharded():
+            if item_log_q is not None or item_embeddings.shape[0] != user_embedding.shape[0]:
+                raise NotImplementedError("log-Q correction / extra negatives are not implemented for row-sharded models")
             return self._sharded_training_loss(user_embedding, item_embeddings, position, labels)
+        item_bias = None if item_log_q is None else -item_log_q
         hook_is_identity = type(self).debias_net_user_value is TwoTowerBaseRetrieval.debias_net_user_value
         T = self.user_value_weights.numel()
         B = user_embedding.shape[0]
@@ -221,13 +230,22 @@ class TwoTowerBaseRetrieval(nn.Module):
         weighted = labels.dim() == 2 and labels.shape[1] == T and labels.shape[0] == B
         if hook_is_identity and ops.labels_fusable(labels) and (weighted or plain_mean):
             lab = labels if weighted else None
-            if ops.fused_loss_supported(user_embedding, item_embeddings, lab, self.user_value_weights):
+            if ops.fused_loss_supported(user_embedding, item_embeddings, lab, self.user_value_weights, item_bias):
                 # the loss head inside the launch that finishes the logits forward (one op, two launches fewer)
+                if item_bias is not None:
+                    return ops.InBatchSoftmaxWeightedLoss.apply(user_embedding, item_embeddings, lab, self.user_value_weights,
+                                                                item_bias)
                 return ops.InBatchSoftmaxWeightedLoss.apply(user_embedding, item_embeddings, lab, self.user_value_weights)
-            row_ce = ops.InBatchSoftmaxCE.apply(user_embedding, item_embeddings, 0)  # [B]
+            row_ce = self._row_ce(user_embedding, item_embeddings, item_bias)  # [B]
             return ops.WeightedMeanLoss.apply(row_ce, lab, self.user_value_weights)
-        row_ce = ops.InBatchSoftmaxCE.apply(user_embedding, item_embeddings, 0)  # [B]
+        row_ce = self._row_ce(user_embedding, item_embeddings, item_bias)  # [B]
         return self._loss_head(row_ce, labels, position, user_embedding)
+
+    @staticmethod
+    def _row_ce(user_embedding, item_embeddings, item_bias) -> torch.Tensor:
+        if item_bias is None:
+            return ops.InBatchSoftmaxCE.apply(user_embedding, item_embeddings, 0)
+        return ops.InBatchSoftmaxCE.apply(user_embedding, item_embeddings, 0, None, item_bias)
 
     def _loss_head(self, row_ce, labels, position, user_embedding) -> torch.Tensor:
         """General loss head: exactly the reference's expressions on [B]-sized tensors (ref :322-345), so every
@@ -324,8 +342,22 @@ class TwoTowerBaseRetrieval(nn.Module):
         item_features: torch.Tensor,  # [B, II]
         position: torch.Tensor,  # [B]
         labels: torch.Tensor,  # [B, T]
+        item_log_q: Optional[torch.Tensor] = None,  # [B]
+        negative_item_id: Optional[torch.Tensor] = None,  # [Bn]
+        negative_item_features: Optional[torch.Tensor] = None,  # [Bn, II]
+        negative_log_q: Optional[torch.Tensor] = None,  # [Bn]
     ) -> torch.Tensor:
-        """Scalar training loss with an autograd graph (ref :349-394)."""
+        """Scalar training loss with an autograd graph (ref :349-394).
+
+        The four keywords behind the reference's seven arguments (all default None: the reference's loss, unchanged):
+        ``item_log_q`` -- log sampling probability of each batch item, subtracted from its logit column (log-Q
+        correction, see compute_training_loss); ``negative_item_id`` / ``negative_item_features`` -- Bn extra items that
+        go through the item tower with the batch's own and widen the logits to [B, B + Bn] (mixed negative sampling; the
+        positives stay on the leading diagonal, the extra rows get item-tower and table-row gradients like any other
+        item); ``negative_log_q`` -- their log sampling probabilities (needed whenever ``item_log_q`` is given)."""
+        if any(t is not None for t in (item_log_q, negative_item_id, negative_item_features, negative_log_q)):
+            item_id, item_features, item_log_q = self._with_negatives(
+                item_id, item_features, item_log_q, negative_item_id, negative_item_features, negative_log_q)
         self._announce_lookups(user_id, user_history, item_id)
         if self._sharded():
             # the item tower FIRST (the towers are independent): autograd then runs the user tower's backward before the
@@ -359,9 +391,10 @@ class TwoTowerBaseRetrieval(nn.Module):
             ref = getattr(self.item_id_embedding_arch.weight, "_tt_optimizer", None)
             opt = ref() if ref is not None else None
             no_sweep = opt is not None and getattr(opt, "lazy", False)
-            pair = self._tower_pair_args(user_id, user_features, item_id, item_features) if (tuned and no_sweep) else None
+            same_rows = item_id.shape[0] == user_id.shape[0]  # extra negatives: the pair kernels take one row count
+            pair = self._tower_pair_args(user_id, user_features, item_id, item_features) if (tuned and no_sweep and same_rows) else None
             fork = ops.AuxFork(user_id.device, rows=user_id.numel() if (tuned and pair is None) else 0)
-            if tuned and pair is None and not fork.on:
+            if tuned and pair is None and not fork.on and same_rows:
                 pair = self._tower_pair_args(user_id, user_features, item_id, item_features)
             if pair is not None:
                 N.oob.poll(user_id.device)
@@ -372,6 +405,32 @@ class TwoTowerBaseRetrieval(nn.Module):
                     fork.uses(item_id, item_features)
                     item_embeddings = self.compute_item_embeddings(item_id, item_features)
                 item_embeddings = fork.joined(item_embeddings)
+        # (a subclass's compute_training_loss with the reference's signature keeps working while the term is unused)
+        extra = {} if item_log_q is None else {"item_log_q": item_log_q}
         return self.compute_training_loss(
-            user_embedding=user_embedding, item_embeddings=item_embeddings, position=position, labels=labels
+            user_embedding=user_embedding, item_embeddings=item_embeddings, position=position, labels=labels, **extra
         )
+
+    def _with_negatives(self, item_id, item_features, item_log_q, negative_item_id, negative_item_features, negative_log_q):
+        """(item ids, item features, log q) of the candidate block [batch items | extra negatives], concatenated BEFORE
+        the lookups are announced: the optimiser is told one [B + Bn] item block, in the order the forward looks it up."""
+        if self._sharded():
+            raise NotImplementedError("train_forward: item_log_q / negative_* are not implemented for row-sharded models "
+                                      "(the all-gathered item block would need the gathered log q and diag_offset = rank * (B + Bn))")
+        if (negative_item_id is None) != (negative_item_features is None):
+            raise ValueError("train_forward: negative_item_id and negative_item_features come together")
+        if negative_item_id is None:
+            if negative_log_q is not None:
+                raise ValueError("train_forward: negative_log_q without negative_item_id / negative_item_features")
+            return item_id, item_features, item_log_q
+        if (item_log_q is None) != (negative_log_q is None):
+            raise ValueError("train_forward: with extra negatives give both item_log_q and negative_log_q or neither "
+                             "(a half-corrected row is never wanted)")
+        if negative_item_id.dim() != 1 or negative_item_features.dim() != 2 or \
+                negative_item_features.shape[0] != negative_item_id.shape[0]:
+            raise ValueError("train_forward: negative_item_id [Bn], negative_item_features [Bn, II]")
+        item_id = torch.cat([item_id, negative_item_id.to(item_id.dtype)])
+        item_features = torch.cat([item_features, negative_item_features.to(item_features.dtype)])
+        if item_log_q is not None:
+            item_log_q = torch.cat([item_log_q, negative_log_q])
+        return item_id, item_features, item_log_q

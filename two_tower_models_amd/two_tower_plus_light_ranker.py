@@ -118,8 +118,14 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
     # ------------------------------------------------------------------ training
     def train_forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor,
                       item_id: torch.Tensor, item_features: torch.Tensor, position: torch.Tensor,
-                      labels: torch.Tensor) -> torch.Tensor:
-        """MIPS term + light ranker term (ref :211-340).  No host synchronisation: GraphedTrainStep captures it."""
+                      labels: torch.Tensor, item_log_q=None, negative_item_id=None, negative_item_features=None,
+                      negative_log_q=None) -> torch.Tensor:
+        """MIPS term + light ranker term (ref :211-340).  No host synchronisation: GraphedTrainStep captures it.
+        The log-Q / extra-negative keywords of TwoTowerBaseRetrieval.train_forward are refused: the ranker term scores
+        the impressed item only and has no corrected form here."""
+        if any(t is not None for t in (item_log_q, negative_item_id, negative_item_features, negative_log_q)):
+            raise NotImplementedError("TwoTowerPlusLightRanker.train_forward: item_log_q / negative_* are not implemented "
+                                      "for the light-ranker model")
         self._check_unsharded("train_forward")
         self._announce_lookups(user_id, user_history, item_id)
         u, R = self.compute_user_embedding(user_id, user_features, user_history)  # [B, DI], [B, NU, DI]
