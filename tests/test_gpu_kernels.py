@@ -595,6 +595,7 @@ def test_adam_table_equals_dense_adam(T, n_rows, D, n1, n2):
     p_ref, m_ref, v_ref = W.clone(), torch.zeros_like(W), torch.zeros_like(W)
     Wd, Md, Vd = W.to(DEV), torch.zeros(n_rows, D, device=DEV), torch.zeros(n_rows, D, device=DEV)
     hyper = torch.tensor([1e-3, 0.9, 0.999, 1e-8, 0, 0, 0, 0], dtype=torch.float64, device=DEV)
+    grads = []
     for step in range(1, 4):
         blocks, dense = [], torch.zeros(n_rows, D)
         for k, n in enumerate((n1, n2)):
@@ -605,6 +606,7 @@ def test_adam_table_equals_dense_adam(T, n_rows, D, n1, n2):
             dense.index_add_(0, ids, rows)
             blocks.append(ops.RowGrad(ids.to(DEV), rows.to(DEV)))
         R.adam_update(p_ref, dense, m_ref, v_ref, step)
+        grads.append(dense)
         N.check(lib.tt_adam_advance(hyper.data_ptr(), N.stream()), "advance")
         plan = ops.RowPlan.from_grads(blocks, n_rows)
         wsp, wsn = ops._ws(torch.device(DEV), lib.tt_adam_table_workspace_bytes(plan.n, D), "adam_side")
@@ -617,6 +619,10 @@ def test_adam_table_equals_dense_adam(T, n_rows, D, n1, n2):
     assert torch.allclose(Md.cpu(), m_ref, atol=1e-7, rtol=1e-4)
     assert torch.allclose(Vd.cpu(), v_ref, atol=1e-9, rtol=1e-4)
     assert float(hyper[4]) == 3.0
+    # ... and within the float64 reference's bounds (adam_ref.py: 4 x what the oracle itself needs), every element
+    import adam_ref as AR
+    ref = AR.bounds(W, torch.zeros_like(W), torch.zeros_like(W), grads, 1)
+    assert AR.violations((Wd, Md, Vd), ref) == {"p": 0, "m": 0, "v": 0}, AR.ratios((Wd, Md, Vd), ref)
 
 
 @pytest.mark.parametrize("n_rows,D,n", [(5003, 128, 900), (1000, 64, 700), (777, 32, 300), (300, 256, 100), (40000, 128, 30000)])

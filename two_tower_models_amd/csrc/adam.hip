@@ -66,11 +66,31 @@ __device__ __forceinline__ void adam_elem_zero_grad(float& p, float& m, float& v
   p = fmaf(c.neg_step_size, adam_ratio(m, v, c), p);
 }
 
+// b^t for a step count t in double-double arithmetic (exponentiation by squaring, every product with its fma error term),
+// rounded to double once at the end.  The library's pow() is good to an ulp or two, and 1 - b^t is the bias correction
+// torch.optim.Adam computes on the host with a correctly rounded pow: at step 1000 sqrt(1 - 0.999^t) came out one ulp
+// above the host's (tests/test_gpu_adam.py compares hyper[4..6] with the host's doubles).  Relative error here:
+// ~t * 2^-104.  An underflowing power loses its low part, which 1 - b^t does not see.
+__device__ __forceinline__ void dd_mul(double& ah, double& al, double bh, double bl) {
+#pragma clang fp contract(off)  // p must be the ROUNDED product everywhere below: fused into p + e it would count its error twice
+  const double p = ah * bh;
+  const double e = fma(ah, bh, -p) + fma(ah, bl, al * bh);
+  ah = p + e;
+  al = e - (ah - p);
+}
+__device__ __forceinline__ double pow_steps(double b, double step) {
+  double rh = 1.0, rl = 0.0, bh = b, bl = 0.0;
+  for (unsigned long long e = (unsigned long long)step; e; e >>= 1) {
+    if (e & 1) dd_mul(rh, rl, bh, bl);
+    dd_mul(bh, bl, bh, bl);
+  }
+  return rh;
+}
 // step-dependent constants exactly as load_hyper() hands them to the kernels
 __device__ __forceinline__ void step_consts_from_doubles(double lr, double b1, double b2, double step,
                                                          double& h5, double& h6) {
-  h5 = lr / (1.0 - pow(b1, step));
-  h6 = sqrt(1.0 - pow(b2, step));
+  h5 = lr / (1.0 - pow_steps(b1, step));
+  h6 = sqrt(1.0 - pow_steps(b2, step));
 }
 // tab (optional): per-step constants for the deferred schedule, tab[2j] = (float)(-h5_j),
 // tab[2j+1] = (float)(1 / h6_j) -- the values every dense kernel of step j saw

@@ -58,6 +58,10 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss = self._body()
+        if getattr(optimizer, "lazy", False):
+            # the deferred schedule's kernels were captured with the optimiser's step-constant table: eager steps taken
+            # between replays must go on using (and filling) that very table (DenseExactAdam._advance_lazy)
+            optimizer._tab_pinned = True
 
     def _body(self) -> torch.Tensor:
         loss = self.model.train_forward(*self.static_inputs)

@@ -63,6 +63,7 @@ from . import ops
 
 
 _RELEASE_AT_LOGITS = True  # a sweep held for the backward logits kernel is released BY that kernel's Function (A/B switch)
+_TAB_MIN_STEPS = 1 << 16  # deferred schedule: steps the per-step constant table holds at first (it doubles as needed; tests lower it)
 _SPLIT_MIN_IDS = 65536  # looked-up rows per step from which the moments leave the main stream's begin launch (tests lower it)
 _MARK_ROWS = True  # ... and are not parked at all: the sweep steps over the step's rows (tools/ab_c3.py flips it)
 _HOLD_SWEEP = True  # (tools/ab_c3.py flips it: the held-back sweep start against the immediate one, same process, same box)
@@ -128,6 +129,7 @@ class DenseExactAdam(torch.optim.Optimizer):
         self._last_step: Dict[int, torch.Tensor] = {}
         self._tab: Optional[torch.Tensor] = None
         self._tab_steps = 0
+        self._tab_pinned = False  # a captured graph reads the table (graphs.GraphedTrainStep): it is never replaced from then on
         self._host_steps = 0  # steps taken, counted on the host (no device sync)
         self._resume_step = 0  # step count adopted from a loaded checkpoint
         self._prefetch_done: Optional[torch.cuda.Event] = None
@@ -183,7 +185,7 @@ class DenseExactAdam(torch.optim.Optimizer):
             # a checkpoint holds flushed tables: every row is current for the step it was taken at
             for p in self._tables:
                 self._last_step[id(p)] = torch.full((p.shape[0],), start, dtype=torch.int32, device=dev)
-            self._tab_steps = max(1 << 16, 2 * (start + 2))
+            self._tab_steps = max(_TAB_MIN_STEPS, 2 * (start + 2))
             self._tab = torch.zeros(2 * self._tab_steps, dtype=torch.float32, device=dev)
         self._ready = True
 
@@ -373,7 +375,14 @@ class DenseExactAdam(torch.optim.Optimizer):
         self._ready = False  # device-side state is rebuilt around the loaded moments
 
     def _advance_lazy(self) -> None:
-        if self._host_steps + 2 >= self._tab_steps:  # grow the per-step constant table (x2)
+        # Grow the per-step constant table (x2) -- unless a graph has captured it, or is capturing it right now.  A captured
+        # graph keeps the pointer and the size of its capture: its replays write their steps' constants into THAT table (none
+        # beyond its size) and read them from it, so a replacement would miss every replayed step (an eager step or a flush
+        # after it would replay idle rows with constants of zero) and the graph would read a table the allocator has taken
+        # back.  Inside a capture the allocation and the copy would become nodes of the graph.  A table that stops growing
+        # costs time, never bits: the kernels compute the constants of a step beyond it themselves (replay_consts).
+        if (self._host_steps + 2 >= self._tab_steps and not self._tab_pinned
+                and not torch.cuda.is_current_stream_capturing()):
             bigger = torch.zeros(4 * self._tab_steps, dtype=torch.float32, device=self._tab.device)
             bigger[: 2 * self._tab_steps].copy_(self._tab)
             self._tab, self._tab_steps = bigger, 2 * self._tab_steps
