@@ -336,6 +336,185 @@ def test_side_stream_weight_gradients_equal_inline_ones(golden):
             assert torch.equal(got2[n], want2[n]), (n, "shared")
 
 
+_ENCODER_ENTRY_POINTS = ("tt_hist_embed_pool", "tt_gemm_f32", "tt_gemm_tn_colsum_f32", "tt_attn_fwd", "tt_attn_bwd",
+                         "tt_enc_last_fwd", "tt_enc_last_bwd_data", "tt_enc_last_bwd_weights", "tt_hist_dx_pool_bwd",
+                         "tt_hist_pool_bwd")
+
+
+class _TracingLibrary:
+    """The loaded library with every attribute forwarded; the encoder's entry points append (name, stream, dims) to `log`
+    before they call through: stream = "side" if the call's stream argument (the last one) is the third stream, else "main";
+    dims = (layout, M, N, K) of tt_gemm_f32, (M, N, K) of tt_gemm_tn_colsum_f32, () otherwise."""
+
+    def __init__(self, lib, log, side_stream):
+        self._lib, self._log, self._side_stream = lib, log, side_stream
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name not in _ENCODER_ENTRY_POINTS:
+            return fn
+
+        def traced(*args):
+            dims = ()
+            if name == "tt_gemm_f32":
+                dims = (("NT", "NN", "TN")[args[0]], *args[1:4])
+            elif name == "tt_gemm_tn_colsum_f32":
+                dims = tuple(args[:3])
+            self._log.append((name, "side" if args[-1] == self._side_stream else "main", dims))
+            return fn(*args)
+
+        return traced
+
+
+class _HeldSweepStub:
+    """What HistoryEncoder.forward asks of the table's optimiser: is the held sweep marked, and release it."""
+
+    def __init__(self, log, marked):
+        self.log, self.marked = log, marked
+
+    def held_sweep_is_marked(self):
+        return self.marked
+
+    def release_sweep(self, after=None):
+        self.log.append(("release", self.marked, after is not None))
+
+
+def _encoder_trace(monkeypatch, D, H, heads, L, B, marked=None, generic=False, inline=False):
+    """One forward + loss.backward() of a fresh encoder (every .grad None) -> the host-order list of its library calls.
+    marked None: embedded history [B, H, D]; True / False: a [1000, D] table + ids whose optimiser holds a (marked) sweep."""
+    import warnings
+    import two_tower_models_amd as A
+    from two_tower_models_amd import _native as N, ops
+    assert (N.TT_GEMM_NT, N.TT_GEMM_NN, N.TT_GEMM_TN) == (0, 1, 2)
+    log = []
+    traced = _TracingLibrary(N.load(), log, N.aux_stream(torch.device(DEV)).cuda_stream)
+    monkeypatch.setattr(N, "load", lambda: traced)
+    monkeypatch.setattr(ops, "_ENC_GENERIC", generic)
+    monkeypatch.setattr(ops, "_SIDE_GRADS", not inline)
+    torch.manual_seed(0)
+    enc = A.UserHistoryEncoder(D, H, heads, L, True).to(DEV)
+    with warnings.catch_warnings():  # note_generic's once-per-process RuntimeWarning (odd widths): whoever meets it first
+        warnings.simplefilter("ignore", RuntimeWarning)
+        if marked is None:
+            y = enc(torch.randn(B, H, D, device=DEV).requires_grad_(True))
+        else:
+            table = torch.randn(1000, D, device=DEV).requires_grad_(True)
+            stub = _HeldSweepStub(log, marked)
+            table._tt_optimizer = lambda: stub
+            y = enc.encode_ids(table, torch.randint(0, 1000, (B, H), device=DEV))
+        (y * torch.randn_like(y)).sum().backward()
+    torch.cuda.synchronize()
+    return log
+
+
+def _k(name, stream="main"):
+    return (name, stream, ())
+
+
+def _g(stream, *dims):
+    return ("tt_gemm_f32", stream, dims)
+
+
+def _w(stream, *dims):
+    return ("tt_gemm_tn_colsum_f32", stream, dims)
+
+
+def _r(marked, after):
+    return ("release", marked, after)
+
+
+# case -> ((D, H, heads, L, B), options of _encoder_trace, the trace).  The traces are what the commit BEFORE the encoder's
+# layer plan produced (dad9cd8), pasted: they pin the enqueue order, the stream of every launch and the sweep's release point
+# that the measurements quoted in ops.py settled.
+_ENCODER_TRACES = {
+    "default": ((128, 50, 4, 3, 8), dict(), [
+        _k("tt_hist_embed_pool"), _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128),
+        _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128), _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"),
+        _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"), _k("tt_enc_last_fwd"), _k("tt_enc_last_bwd_data"),
+        _k("tt_enc_last_bwd_weights", "side"), _k("tt_attn_bwd"), _w("side", 384, 128, 400),
+        _g("main", "NN", 400, 128, 384), _k("tt_attn_bwd"), _w("side", 384, 128, 400), _k("tt_hist_dx_pool_bwd"),
+        _g("main", "NN", 400, 128, 384), _g("main", "NT", 384, 128, 128), _g("main", "NT", 384, 128, 1),
+        _g("main", "TN", 128, 128, 384), _g("main", "NN", 1, 128, 384), _g("main", "NT", 384, 128, 128),
+        _g("main", "NT", 384, 128, 1), _g("main", "TN", 128, 128, 384), _g("main", "NN", 1, 128, 384),
+        _k("tt_hist_pool_bwd"),
+    ]),
+    "one layer": ((128, 50, 4, 1, 4), dict(), [
+        _k("tt_hist_embed_pool"), _k("tt_enc_last_fwd"), _k("tt_enc_last_bwd_data"), _k("tt_enc_last_bwd_weights", "side"),
+        _k("tt_hist_pool_bwd"),
+    ]),
+    "odd widths": ((40, 7, 4, 2, 5), dict(), [
+        _k("tt_hist_embed_pool"), _g("side", "NN", 120, 40, 40), _g("side", "NT", 1, 120, 40),
+        _g("main", "NT", 35, 120, 40), _k("tt_attn_fwd"), _g("main", "NT", 35, 120, 40), _k("tt_attn_fwd"),
+        _g("main", "NT", 5, 40, 40), _w("main", 40, 40, 5), _g("main", "NN", 5, 40, 40), _k("tt_attn_bwd"),
+        _w("side", 120, 40, 35), _g("main", "NN", 35, 40, 120), _k("tt_attn_bwd"), _w("side", 120, 40, 35),
+        _k("tt_hist_dx_pool_bwd"), _g("main", "NN", 35, 40, 120), _g("main", "NT", 120, 40, 40),
+        _g("main", "NT", 120, 40, 1), _g("main", "TN", 40, 40, 120), _g("main", "NN", 1, 40, 120), _k("tt_hist_pool_bwd"),
+    ]),
+    "plain": ((128, 50, 4, 3, 8), dict(generic=True), [
+        _k("tt_hist_embed_pool"), _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"), _g("main", "NT", 400, 128, 128),
+        _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"), _g("main", "NT", 400, 128, 128),
+        _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"), _g("main", "NT", 8, 128, 128), _w("main", 128, 128, 8),
+        _g("main", "NN", 8, 128, 128), _k("tt_attn_bwd"), _w("side", 384, 128, 400), _g("main", "NN", 400, 128, 384),
+        _w("side", 128, 128, 400), _g("main", "NN", 400, 128, 128), _k("tt_attn_bwd"), _w("side", 384, 128, 400),
+        _g("main", "NN", 400, 128, 384), _w("side", 128, 128, 400), _g("main", "NN", 400, 128, 128), _k("tt_attn_bwd"),
+        _w("side", 384, 128, 400), _g("main", "NN", 400, 128, 384), _k("tt_hist_pool_bwd"),
+    ]),
+    "pool epilogue": ((128, 32, 4, 2, 512), dict(), [
+        _k("tt_hist_embed_pool"), _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128),
+        _g("main", "NT", 16384, 384, 128), _k("tt_attn_fwd"), _k("tt_enc_last_fwd"), _k("tt_enc_last_bwd_data"),
+        _k("tt_enc_last_bwd_weights", "side"), _k("tt_attn_bwd"), _w("side", 384, 128, 16384), _k("tt_hist_dx_pool_bwd"),
+        _g("main", "NT", 384, 128, 128), _g("main", "NT", 384, 128, 1), _g("main", "TN", 128, 128, 384),
+        _g("main", "NN", 1, 128, 384),
+    ]),
+    "marked sweep": ((128, 50, 4, 3, 8), dict(marked=True), [
+        _k("tt_hist_embed_pool"), _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128),
+        _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128), _g("main", "NT", 400, 384, 128), _r(True, True),
+        _k("tt_attn_fwd"), _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"), _k("tt_enc_last_fwd"),
+        _k("tt_enc_last_bwd_data"), _k("tt_enc_last_bwd_weights", "side"), _k("tt_attn_bwd"), _w("side", 384, 128, 400),
+        _g("main", "NN", 400, 128, 384), _k("tt_attn_bwd"), _w("side", 384, 128, 400), _k("tt_hist_dx_pool_bwd"),
+        _g("main", "NN", 400, 128, 384), _g("main", "NT", 384, 128, 128), _g("main", "NT", 384, 128, 1),
+        _g("main", "TN", 128, 128, 384), _g("main", "NN", 1, 128, 384), _g("main", "NT", 384, 128, 128),
+        _g("main", "NT", 384, 128, 1), _g("main", "TN", 128, 128, 384), _g("main", "NN", 1, 128, 384),
+        _k("tt_hist_pool_bwd"),
+    ]),
+    "unmarked sweep": ((128, 50, 4, 3, 8), dict(marked=False), [
+        _k("tt_hist_embed_pool"), _r(False, False), _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128),
+        _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128), _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"),
+        _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"), _k("tt_enc_last_fwd"), _k("tt_enc_last_bwd_data"),
+        _k("tt_enc_last_bwd_weights", "side"), _k("tt_attn_bwd"), _w("side", 384, 128, 400),
+        _g("main", "NN", 400, 128, 384), _k("tt_attn_bwd"), _w("side", 384, 128, 400), _k("tt_hist_dx_pool_bwd"),
+        _g("main", "NN", 400, 128, 384), _g("main", "NT", 384, 128, 128), _g("main", "NT", 384, 128, 1),
+        _g("main", "TN", 128, 128, 384), _g("main", "NN", 1, 128, 384), _g("main", "NT", 384, 128, 128),
+        _g("main", "NT", 384, 128, 1), _g("main", "TN", 128, 128, 384), _g("main", "NN", 1, 128, 384),
+        _k("tt_hist_pool_bwd"),
+    ]),
+    "marked, one layer": ((128, 50, 4, 1, 4), dict(marked=True), [
+        _k("tt_hist_embed_pool"), _k("tt_enc_last_fwd"), _r(True, False), _k("tt_enc_last_bwd_data"),
+        _k("tt_enc_last_bwd_weights", "side"), _k("tt_hist_pool_bwd"),
+    ]),
+    "in line": ((128, 50, 4, 3, 8), dict(inline=True), [
+        _k("tt_hist_embed_pool"), _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128),
+        _g("side", "NN", 384, 128, 128), _g("side", "NT", 1, 384, 128), _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"),
+        _g("main", "NT", 400, 384, 128), _k("tt_attn_fwd"), _k("tt_enc_last_fwd"), _k("tt_enc_last_bwd_data"),
+        _k("tt_enc_last_bwd_weights"), _k("tt_attn_bwd"), _w("main", 384, 128, 400), _g("main", "NN", 400, 128, 384),
+        _k("tt_attn_bwd"), _w("main", 384, 128, 400), _k("tt_hist_dx_pool_bwd"), _g("main", "NN", 400, 128, 384),
+        _g("main", "NT", 384, 128, 128), _g("main", "NT", 384, 128, 1), _g("main", "TN", 128, 128, 384),
+        _g("main", "NN", 1, 128, 384), _g("main", "NT", 384, 128, 128), _g("main", "NT", 384, 128, 1),
+        _g("main", "TN", 128, 128, 384), _g("main", "NN", 1, 128, 384), _k("tt_hist_pool_bwd"),
+    ]),
+}
+
+
+@pytest.mark.parametrize("case", list(_ENCODER_TRACES))
+def test_encoder_call_trace(case, monkeypatch):
+    """The sequence of library calls of one encoder forward + backward, with the stream each is queued on, the GEMM
+    shapes and the point where a held table sweep is released, is the recorded one entry for entry."""
+    shape, options, want = _ENCODER_TRACES[case]
+    got = _encoder_trace(monkeypatch, *shape, **options)
+    first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+    assert got == want, (case, "first difference at entry", first, got[first:first + 3], want[first:first + 3])
+
+
 @pytest.mark.parametrize("kind,name", [("base", "g2_base_aligned"), ("hist", "g4_hist_d128")])
 @pytest.mark.parametrize("schedule", ["forward", "zero_grad", "serial", "lazy", "torch"])
 def test_item_tower_on_the_third_stream_is_bit_identical_to_one_stream(golden, monkeypatch, kind, name, schedule):

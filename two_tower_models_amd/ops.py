@@ -53,8 +53,6 @@ def _ws(dev: torch.device, nbytes: int, slot: str = "ws") -> Tuple[Optional[int]
 # returns with the caller's stream ordered after both (AuxFork.joined).
 # Measured (one process, alternating blocks, tools/ab_c3.py): C2 1.12 -> 1.09 ms, history model +-0, deferred P-shape step
 # 1.36 -> 1.30 ms.  TT_TOWERS_SERIAL=1: one stream (A/B).
-_FOLD_ASIDE = True  # (likewise: the composed-weight products of the encoder's forward on the third stream / between the layers)
-_EL_WGRAD_SIDE = True  # (tools/ab_c3.py flips it: the collapsed last layer's weight half on the third stream / in line)
 _CONCURRENT_TOWERS = os.environ.get("TT_TOWERS_SERIAL") is None
 _FORK_MIN_ROWS = 2048  # (tests lower it: the golden batches are small)
 _aux_forks = [0]  # forks whose backward pass has not ended yet (two models' steps may interleave; a forward that never gets a
@@ -1342,6 +1340,202 @@ def _attn_fwd(qkv, B, H, D, heads):
     return ctx_t, lse
 
 
+# The layer plan.  A layer that reads the previous layer's attention CONTEXT c runs on c with the composed weights of
+# `fold_weights`: x_l = c W_o^T + b_o never exists, and layer l - 1 has no out-projection.
+# A collapsed last layer implies `not _ENC_GENERIC`, and it composes its weights exactly as a full layer does, so the kind of
+# layer drops out: layer l reads the context  <=>  it has a previous layer and the plain composition was not asked for.
+def _reads_context(l: int) -> bool:
+    return not _ENC_GENERIC and l >= 1
+
+
+def _compose_aside(dev, layer_params, layers):
+    """-> {l: (W_eff, b_eff, event)} for the `layers` that read the context; empty while a hipGraph is being captured."""
+    # The composed weights depend on nothing but the parameters: all boundaries' products (two 10-us library launches each,
+    # 20 - 25 us each next to the table sweep) are queued on the third stream HERE, underneath the history gather and the first
+    # layer, instead of between the layers on the main stream; a layer waits for its own pair's event.  (Allocated on the third
+    # stream, read on the main one until the backward pass ends: every later use of the third stream starts by waiting for the
+    # main one, see AuxFork.)
+    queued = {}
+    if layers and dev.type == "cuda" and not torch.cuda.is_current_stream_capturing():
+        top, aux_s = torch.cuda.Event(), N.aux_stream(dev)
+        top.record()
+        aux_s.wait_event(top)
+        with torch.cuda.stream(aux_s):
+            for l in layers:
+                we, be = fold_weights(*layer_params[4 * l: 4 * l + 2], *layer_params[4 * l - 2: 4 * l], slot="ws_side_f")
+                ready = torch.cuda.Event()
+                ready.record(aux_s)
+                queued[l] = (we, be, ready)
+    return queued
+
+
+def _enc_layer_fwd(l, L, dims, x, w, b, w_out, b_out, out, sweep_opt):
+    """A full layer on (w, b), its own in-projection or the composed one -> (the next layer's input, tensors to save)."""
+    B, H, D, heads = dims
+    qkv = torch.empty(B * H, 3 * D, dtype=torch.float32, device=x.device)
+    gemm(N.TT_GEMM_NT, x, w, qkv, B * H, 3 * D, D, bias=b)
+    if sweep_opt is not None:  # the optimiser whose held, marked table sweep starts HERE
+        # Measured over every launch of the C3 step as the release point, each at its best sweep width
+        # (tools/sweep_release_scan.py, profiles/r06_sweep_release_scan.txt): behind the history gather 3.14-3.15 ms,
+        # behind THIS product 3.11-3.12, behind the attention kernel 3.22-3.25, behind the second layer's product
+        # 3.18-3.22, later 3.2-3.5; parked rows (which start the sweep about here: the moments' gather ran in front of
+        # it) 3.32-3.37
+        started = torch.cuda.Event()
+        started.record()
+        sweep_opt.release_sweep(after=started)
+    ctx_t, lse = _attn_fwd(qkv, B, H, D, heads)
+    if l + 1 < L and _reads_context(l + 1):
+        x_next = ctx_t  # no out-projection here: the next layer takes the context (fold_weights / csrc/encoder_last.hip, PREV)
+    elif l + 1 < L:
+        x_next = torch.empty(B * H, D, dtype=torch.float32, device=x.device)
+        gemm(N.TT_GEMM_NT, ctx_t, w_out, x_next, B * H, D, D, bias=b_out)
+    else:  # last layer, not collapsed: rows b*H + 0 only, straight into out[:, 0, :]
+        x_next = None
+        gemm(N.TT_GEMM_NT, ctx_t.view(B, H * D)[:, :D], w_out, out[:, 0, :], B, D, D, bias=b_out)
+    return x_next, [x, qkv, ctx_t, lse]
+
+
+def _enc_last_fwd(dims, x, w, b, w_out, b_out, out):
+    """The collapsed last layer on (w, b) as for a full layer; writes out[:, 0, :] -> tensors to save."""
+    # the last layer is consumed at row 0 only: one query per (sample, head), and its K / V projections fold into two D-wide
+    # vectors per (sample, head) -- x is read once, no [B*H, 2D] projection (csrc/encoder_last.hip)
+    B, H, D, heads = dims
+    dev = x.device
+    q0 = torch.empty(B, D, dtype=torch.float32, device=dev)
+    tq = torch.empty(B, heads, D, dtype=torch.float32, device=dev)
+    probs = torch.empty(B, heads, H, dtype=torch.float32, device=dev)
+    xbar = torch.empty(B, heads, D, dtype=torch.float32, device=dev)
+    ctx0 = torch.empty(B, D, dtype=torch.float32, device=dev)
+    N.check(N.load().tt_enc_last_fwd(x.data_ptr(), B, H, D, heads, w.contiguous().data_ptr(), b.contiguous().data_ptr(),
+                                     w_out.contiguous().data_ptr(), b_out.contiguous().data_ptr(), out.data_ptr(), 2 * D,
+                                     q0.data_ptr(), tq.data_ptr(), probs.data_ptr(), xbar.data_ptr(), ctx0.data_ptr(),
+                                     N.stream()), "tt_enc_last_fwd")
+    return [x, q0, tq, probs, xbar, ctx0]
+
+
+def _enc_wgrad(dy, xin, dW, tag, leaves, hold=()):
+    """dW = dy^T xin and db for the Parameters `leaves`, off the critical path (run_on_side) -> (db, whether it went aside)."""
+    db = torch.empty(dW.shape[0], dtype=torch.float32, device=dy.device)
+    aside = run_on_side(dy.device, lambda on_side: gemm_tn_colsum(dy, xin, dW, db=db, slot=("ws_side_" + tag) if on_side else "ws"),
+                        hold=(dy, xin) + hold, leaves=leaves)
+    return db, aside
+
+
+def _composed_boundary_grads(G, s, w_in, w_po, b_po, aside):
+    """G = dL/dW_eff, s = dL/db_eff of a layer that read the context (`aside`: they are being written on the third stream)
+    -> (dW_in, (dW_out, db_out) of the layer below, the tail job that computes them: fold_weight_grads)."""
+    # The tail job runs at the END of the backward pass on the main stream.  Issued at once on the side stream, these four
+    # 10-us products sat behind the persistent attention-backward workgroups for 0.45 ms and pushed the streaming weight
+    # gradients that much later; in line between one layer's G and the next one's they sat next to the data path's heaviest
+    # kernels, 245 us for 60 us of work, and the side stream finished 250 us after the main one
+    D, dev = w_po.shape[0], G.device
+    dW_in = torch.empty(3 * D, D, dtype=torch.float32, device=dev)
+    dW_po = torch.empty(D, D, dtype=torch.float32, device=dev)
+    db_po = torch.empty(D, dtype=torch.float32, device=dev)
+    written = None
+    if aside:  # the tail job (main stream) waits for exactly the product that writes G
+        written = torch.cuda.Event()
+        written.record(N.aux_stream(dev))
+
+    def tail_job():
+        if written is not None:
+            torch.cuda.current_stream().wait_event(written)
+        fold_weight_grads(G, s, w_in, w_po, b_po, dW_in, dW_po, db_po)
+
+    return dW_in, (dW_po, db_po), tail_job
+
+
+def _enc_last_bwd(l, dims, layer_params, leaves, kept, w_eff, d_out):
+    """-> (dx, [dW_in, db_in, dW_out, db_out], (dW_out, db_out) of the layer below or None, tail job or None)."""
+    B, H, D, heads = dims
+    lib, dev = N.load(), d_out.device
+    w_in, _, w_out, _ = layer_params[4 * l: 4 * l + 4]
+    x, q0, tq, probs, xbar, ctx0 = kept
+    d_recent = d_out[:, 0, :]
+    dx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
+    dW_eff = torch.empty(3 * D, D, dtype=torch.float32, device=dev)  # for the weight the layer ran on: dW_in, or G if composed
+    db_in = torch.empty(3 * D, dtype=torch.float32, device=dev)
+    dW_out = torch.empty(D, D, dtype=torch.float32, device=dev)
+    db_out = torch.empty(D, dtype=torch.float32, device=dev)
+    # one workspace for both halves, whichever stream the weight half runs on (the next user of the slot is the
+    # next step's backward pass, behind the end-of-backward join)
+    wsp, wsn = _ws(dev, lib.tt_enc_last_bwd_workspace_bytes(B, H, D, heads), "enc_last")
+    w_used = w_in if w_eff is None else w_eff  # the composed weight the layer ran on: dx is the gradient of the CONTEXT below
+    N.check(lib.tt_enc_last_bwd_data(x.data_ptr(), B, H, D, heads, w_used.contiguous().data_ptr(),
+                                     w_out.contiguous().data_ptr(), d_recent.data_ptr(), 2 * D, tq.data_ptr(),
+                                     probs.data_ptr(), dx.data_ptr(), wsp, wsn, N.stream()), "tt_enc_last_bwd_data")
+
+    # the weight half ([D, 32] x [32, D] partial products per 32 samples + their reduction) feeds nothing but the
+    # optimiser: third stream (it was the tail of the data kernels: 0.1 ms of the step's critical path)
+    def last_weights(on_side):
+        N.check(lib.tt_enc_last_bwd_weights(x.data_ptr(), B, H, D, heads, d_recent.data_ptr(), 2 * D, q0.data_ptr(),
+                                            xbar.data_ptr(), ctx0.data_ptr(), dW_eff.data_ptr(), db_in.data_ptr(),
+                                            dW_out.data_ptr(), db_out.data_ptr(), wsp, wsn, N.stream()),
+                "tt_enc_last_bwd_weights")
+
+    hold, own = (x, q0, xbar, ctx0, d_out), list(leaves[4 * l + 1: 4 * l + 4])
+    if w_eff is None:
+        run_on_side(dev, last_weights, hold=hold, leaves=own + [leaves[4 * l]])
+        return dx, [dW_eff, db_in, dW_out, db_out], None, None
+    # dW_eff / db_in are the gradients of (W_eff, b_eff): the private G, held like an input, and s.  leaves: the Parameters
+    # whose gradients the side job writes -- G is turned into the two layers' gradients by the tail job, so w_in is not among them
+    aside = run_on_side(dev, last_weights, hold=hold + (dW_eff,), leaves=own)
+    dW_in, below, tail_job = _composed_boundary_grads(dW_eff, db_in, w_in, *layer_params[4 * l - 2: 4 * l], aside)
+    return dx, [dW_in, db_in, dW_out, db_out], below, tail_job
+
+
+def _enc_layer_bwd(l, L, dims, layer_params, leaves, kept, w_eff, d_out, dx, out_grads):
+    """`dx`: the gradient of the layer's output, or of its CONTEXT if the layer above read that and made `out_grads`.
+    -> as _enc_last_bwd, and whether the mean pool's backward is already in dx."""
+    B, H, D, heads = dims
+    lib, dev = N.load(), d_out.device
+    w_in, _, w_out, _ = layer_params[4 * l: 4 * l + 4]
+    x, qkv, ctx_t, lse = kept
+    d_recent, d_pooled = d_out[:, 0, :], d_out[:, 1, :]
+    dW_out = torch.empty(D, D, dtype=torch.float32, device=dev)
+    if out_grads is not None:
+        dW_out, db_out = out_grads
+        d_ctx = dx
+    elif l == L - 1:  # row 0 only
+        rows0 = ctx_t.view(B, H * D)[:, :D]
+        _, db_out = gemm_tn_colsum(d_recent, rows0, dW_out)
+        d_ctx = torch.zeros(B * H, D, dtype=torch.float32, device=dev)
+        gemm(N.TT_GEMM_NN, d_recent, w_out, d_ctx.view(B, H * D)[:, :D], B, D, D)
+    else:
+        db_out, _ = _enc_wgrad(dx, ctx_t, dW_out, "o", leaves[4 * l + 2: 4 * l + 4])
+        d_ctx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
+        gemm(N.TT_GEMM_NN, dx, w_out, d_ctx, B * H, D, D)
+    d_qkv = torch.empty(B * H, 3 * D, dtype=torch.float32, device=dev)
+    N.check(lib.tt_attn_bwd(qkv.data_ptr(), ctx_t.data_ptr(), lse.data_ptr(), d_ctx.data_ptr(), B, H, D,
+                            heads, d_qkv.data_ptr(), N.stream()), "tt_attn_bwd")
+    dx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
+    if w_eff is not None:
+        # x is the previous layer's context c and qkv = c W_eff^T + b_eff:  G = dQKV^T c, s = colsum(dQKV) on the side stream,
+        # d_c = dQKV W_eff on the data path.  The streaming product G is queued BEFORE the data-path product (the side stream
+        # starts where the main one stands now).
+        # (held: INPUTS and the private G only -- never db_in, which is returned as in_proj_bias's gradient: a held
+        # output is CLONED by AccumulateGrad on the main stream before the side stream has written it, ADVICE r4)
+        w_po, b_po = layer_params[4 * l - 2: 4 * l]
+        G = torch.empty(3 * D, D, dtype=torch.float32, device=dev)
+        db_in, aside = _enc_wgrad(d_qkv, x, G, "i", list(leaves[4 * l: 4 * l + 2]) + list(leaves[4 * l - 2: 4 * l]),
+                                  hold=(G, w_po, b_po, w_in, w_eff))
+        dW_in, below, tail_job = _composed_boundary_grads(G, db_in, w_in, w_po, b_po, aside)
+        gemm(N.TT_GEMM_NN, d_qkv, w_eff, dx, B * H, D, 3 * D)
+        return dx, [dW_in, db_in, dW_out, db_out], below, tail_job, False
+    dW_in = torch.empty(3 * D, D, dtype=torch.float32, device=dev)
+    db_in, _ = _enc_wgrad(d_qkv, x, dW_in, "i", leaves[4 * l: 4 * l + 2])
+    rc = N.TT_E_UNSUPPORTED
+    if l == 0 and not _ENC_GENERIC and w_in.is_contiguous():
+        rc = lib.tt_hist_dx_pool_bwd(d_qkv.data_ptr(), w_in.data_ptr(), B, H, D, d_pooled.data_ptr(), 2 * D, dx.data_ptr(),
+                                     N.stream())
+    if rc == N.TT_E_UNSUPPORTED:  # shape not taken: the product, then a read-modify-write pass over dx (tt_hist_pool_bwd)
+        gemm(N.TT_GEMM_NN, d_qkv, w_in, dx, B * H, D, 3 * D)
+    elif rc != 0:
+        N.check(rc, "tt_hist_dx_pool_bwd")
+    # rc == 0: the mean pool's backward rode in the product's epilogue (csrc/gemm_ws16.hip, POOL)
+    return dx, [dW_in, db_in, dW_out, db_out], None, None, rc == 0
+
+
 class HistoryEncoder(_LookupFunction):
     """UserHistoryEncoder.forward (ref:src/user_history_encoder.py:80-121), optionally
     fused with the history id lookup (ref:src/two_tower_with_user_history_encoder.py:105).
@@ -1381,7 +1575,7 @@ class HistoryEncoder(_LookupFunction):
         if ids is not None:
             # the step's big gather is queued: a table sweep the optimiser held back for it may start now (optim.py) -- unless
             # the sweep steps over this step's rows (marked schedule): nothing orders it against the lookups then, and it
-            # starts behind the first in-projection below
+            # starts behind the first full layer's in-projection (_enc_layer_fwd)
             ref = getattr(source, "_tt_optimizer", None)
             opt = ref() if ref is not None else None
             if opt is not None:
@@ -1389,108 +1583,42 @@ class HistoryEncoder(_LookupFunction):
                     sweep_opt = opt
                 else:
                     opt.release_sweep()
-        saved: List[torch.Tensor] = []
-        # the last layer is consumed at row 0 only: one query per (sample, head), K / V projections folded into two D-wide
-        # vectors per (sample, head) (csrc/encoder_last.hip)
+        # the plan: which layers read the previous layer's context (_reads_context), and whether the last one is collapsed
         collapsed_last = (L > 0 and not _ENC_GENERIC and H <= 64 and D // heads <= 64
                           and bool(lib.tt_enc_last_supported(H, D, heads)) and x.data_ptr() % 16 == 0)
-        # ... run on the second-to-last layer's CONTEXT with composed weights (like every other layer boundary below)
-        fold_last = collapsed_last and L >= 2
         dh = D // max(heads, 1)
         if L > 0 and (H > 64 or dh not in (16, 32, 64) or D % 4):
             note_generic("history-encoder attention",
                          f"the matrix-core kernels take H <= 64 and head width in {{16, 32, 64}}; got H = {H}, head width = {dh}: "
                          "VALU attention" + ("" if collapsed_last else ", last layer computed for every position"))
-        fold = not _ENC_GENERIC  # out-projection of layer l composed with the in-projection of layer l + 1
-
-        def folded_in(l):  # layer l (a full layer, not the first) reads the previous layer's context through composed weights
-            return fold and 1 <= l < L and not (l == L - 1 and collapsed_last)
-
-        folded_w = {}
-        # The composed weights depend on nothing but the parameters: all boundaries' products (two 10-us library launches
-        # each, 20 - 25 us each next to the table sweep) are queued on the third stream HERE, underneath the history gather
-        # and the first layer, instead of between the layers on the main stream; a layer waits for its own pair's event.
-        # (Allocated on the third stream, read on the main one until the backward pass ends: every later use of the third
-        # stream starts by waiting for the main one, see AuxFork.)
-        composed = {}
-        will_fold = [l for l in range(L) if folded_in(l) or (l == L - 1 and fold_last)]
-        if will_fold and _FOLD_ASIDE and dev.type == "cuda" and not torch.cuda.is_current_stream_capturing():
-            top, aux_s = torch.cuda.Event(), N.aux_stream(dev)
-            top.record()
-            aux_s.wait_event(top)
-            with torch.cuda.stream(aux_s):
-                for l in will_fold:
-                    w_po, b_po = layer_params[4 * (l - 1) + 2], layer_params[4 * (l - 1) + 3]
-                    we, be = fold_weights(layer_params[4 * l], layer_params[4 * l + 1], w_po, b_po, slot="ws_side_f")
-                    ready = torch.cuda.Event()
-                    ready.record(aux_s)
-                    composed[l] = (we, be, ready)
-
-        def composed_weights(l, w_in, b_in):
-            if l in composed:
-                we, be, ready = composed.pop(l)
-                torch.cuda.current_stream(dev).wait_event(ready)
-                return we, be
-            return fold_weights(w_in, b_in, layer_params[4 * (l - 1) + 2], layer_params[4 * (l - 1) + 3])
-
+        queued = _compose_aside(dev, layer_params, [l for l in range(L) if _reads_context(l)])
+        dims = (B, H, D, heads)
+        saved: List[torch.Tensor] = []
+        # layer that reads the context -> the composed (W_in W_o(prev), bias) it ran on.  The bias is kept only to stay allocated:
+        # both live in the third stream's pool and the main stream reads them, so a block freed while this forward's kernels are
+        # still queued could go to the item tower that AuxFork starts on the third stream without waiting for them
+        ctx.composed = {}
         for l in range(L):
-            w_in, b_in, w_out, b_out = layer_params[4 * l: 4 * l + 4]
+            w, b, w_out, b_out = layer_params[4 * l: 4 * l + 4]
+            if _reads_context(l):
+                if l in queued:
+                    w, b, ready = queued.pop(l)
+                    torch.cuda.current_stream(dev).wait_event(ready)
+                else:
+                    w, b = fold_weights(w, b, *layer_params[4 * l - 2: 4 * l])
+                ctx.composed[l] = (w, b)
             if l == L - 1 and collapsed_last:
-                # the last layer is consumed at row 0 only and its K / V projections fold into two D-wide vectors per
-                # (sample, head): x is read once, no [B*H, 2D] projection (csrc/encoder_last.hip)
-                q0 = torch.empty(B, D, dtype=torch.float32, device=dev)
-                tq = torch.empty(B, heads, D, dtype=torch.float32, device=dev)
-                probs = torch.empty(B, heads, H, dtype=torch.float32, device=dev)
-                xbar = torch.empty(B, heads, D, dtype=torch.float32, device=dev)
-                ctx0 = torch.empty(B, D, dtype=torch.float32, device=dev)
-                w_in_c, w_out_c, b_in_c = w_in.contiguous(), w_out.contiguous(), b_in.contiguous()
-                if fold_last:
-                    # x is the previous layer's CONTEXT c.  q, k, v of this layer are linear in x = c W_o^T + b_o, so the layer
-                    # runs on c with W_eff = W_in W_o, b_eff = W_in b_o + b_in -- the same kernels as for a first layer
-                    w_in_c, b_in_c = composed_weights(l, w_in, b_in)
-                    folded_w[l] = w_in_c
-                N.check(lib.tt_enc_last_fwd(x.data_ptr(), B, H, D, heads, w_in_c.data_ptr(), b_in_c.data_ptr(),
-                                            w_out_c.data_ptr(), b_out.contiguous().data_ptr(), out.data_ptr(), 2 * D,
-                                            q0.data_ptr(), tq.data_ptr(), probs.data_ptr(), xbar.data_ptr(), ctx0.data_ptr(),
-                                            N.stream()), "tt_enc_last_fwd")
-                saved += [x, q0, tq, probs, xbar, ctx0]
-                continue
-            qkv = torch.empty(B * H, 3 * D, dtype=torch.float32, device=dev)
-            if folded_in(l):
-                # x is the previous layer's CONTEXT c: x_l = c W_o^T + b_o never exists, the two Linear maps are composed --
-                #   qkv = c (W_in W_o)^T + (W_in b_o + b_in)          ([3D, D] x [D, D]: 12.6 MFLOP instead of a [B*H, D] x [D, D]
-                # out-projection, and its d_ctx / dW_out products in the backward)
-                w_eff, b_eff = composed_weights(l, w_in, b_in)
-                gemm(N.TT_GEMM_NT, x, w_eff, qkv, B * H, 3 * D, D, bias=b_eff)
-                folded_w[l] = w_eff
+                saved += _enc_last_fwd(dims, x, w, b, w_out, b_out, out)
             else:
-                gemm(N.TT_GEMM_NT, x, w_in, qkv, B * H, 3 * D, D, bias=b_in)
-            if sweep_opt is not None:
-                # Measured over every launch of the C3 step as the release point, each at its best sweep width
-                # (tools/sweep_release_scan.py, profiles/r06_sweep_release_scan.txt): behind the history gather 3.14-3.15 ms,
-                # behind THIS product 3.11-3.12, behind the attention kernel 3.22-3.25, behind the second layer's product
-                # 3.18-3.22, later 3.2-3.5; parked rows (which start the sweep about here: the moments' gather ran in front of
-                # it) 3.32-3.37
-                started = torch.cuda.Event()
-                started.record()
-                sweep_opt.release_sweep(after=started)
+                x, kept = _enc_layer_fwd(l, L, dims, x, w, b, w_out, b_out, out, sweep_opt)
+                saved += kept
                 sweep_opt = None
-            ctx_t, lse = _attn_fwd(qkv, B, H, D, heads)
-            saved += [x, qkv, ctx_t, lse]
-            if (l + 2 == L and fold_last) or folded_in(l + 1):
-                x = ctx_t  # no out-projection here: the next layer takes the context (fold above / csrc/encoder_last.hip, PREV)
-            elif l + 1 < L:
-                x = torch.empty(B * H, D, dtype=torch.float32, device=dev)
-                gemm(N.TT_GEMM_NT, ctx_t, w_out, x, B * H, D, D, bias=b_out)
-            else:  # rows b*H + 0 only, straight into out[:, 0, :]
-                gemm(N.TT_GEMM_NT, ctx_t.view(B, H * D)[:, :D], w_out, out[:, 0, :], B, D, D, bias=b_out)
         if L == 0:
             out[:, 0, :].copy_(x.view(B, H, D)[:, 0, :])
         if sweep_opt is not None:  # no full layer ran
             sweep_opt.release_sweep()
         ctx.dims = (B, H, D, L, heads)
         ctx.collapsed_last = collapsed_last
-        ctx.folded = {l: w for l, w in folded_w.items()}  # layer -> its composed in-projection weight W_in W_o(prev)
         ctx.layer_leaves = tuple(layer_params)  # the Parameter objects themselves (see ops.run_on_side: `leaves`)
         if L > 0 and _caller_grad_mode[0] and any(ctx.needs_input_grad[4:]):  # (grad mode is always off in here: _recording)
             _side_state["encoder"] = True
@@ -1506,161 +1634,33 @@ class HistoryEncoder(_LookupFunction):
         ids = t[0]
         layer_params = t[1: 1 + 4 * L]
         saved = t[1 + 4 * L:]
-        dev = d_out.device
-        lib = N.load()
         d_out = d_out.contiguous()
-        d_recent, d_pooled = d_out[:, 0, :], d_out[:, 1, :]
+        dims, leaves = (B, H, D, heads), ctx.layer_leaves
         grads: List[Optional[torch.Tensor]] = [None] * (4 * L)
-        dx = None  # gradient wrt the current layer's OUTPUT x_{l+1}, [B*H, D]
-        prev_out_grads = None
-        # (fn, event of the side-stream product it consumes or None): the composed boundaries' small weight-gradient products.
-        # They run at the END of this backward, IN LINE on the main stream: by then the main stream has nothing left to do
-        # but wait for the side stream's streaming weight gradients, and the side stream has those still to run
+        dx = None  # gradient wrt the current layer's OUTPUT x_{l+1}, [B*H, D] -- or wrt its context, with `out_grads`
+        out_grads = None  # (dW_out, db_out) of the current layer when the layer above read its context: made by that one
+        # The composed boundaries' small weight-gradient products.  They run at the END of this backward, IN LINE on the main
+        # stream, in creation order: by then the main stream has nothing left to do but wait for the side stream's streaming
+        # weight gradients, and the side stream has those still to run
         tail_jobs = []
         pool_done = False
-        leaf_params = ctx.layer_leaves
-
-        def wgrad(dy, xin, dW, tag, l):  # off the critical path: see run_on_side
-            db = torch.empty(dW.shape[0], dtype=torch.float32, device=dev)
-            k = 4 * l + (0 if tag == "i" else 2)  # the (weight, bias) pair this product is the gradient of
-            run_on_side(dev, lambda on_side: gemm_tn_colsum(dy, xin, dW, db=db, slot=("ws_side_" + tag) if on_side else "ws"),
-                        hold=(dy, xin), leaves=leaf_params[k: k + 2])
-            return db
-
         for l in reversed(range(L)):
-            w_in, b_in, w_out, b_out = layer_params[4 * l: 4 * l + 4]
+            w_eff = ctx.composed.get(l, (None, None))[0]
             if l == L - 1 and ctx.collapsed_last:
-                x, q0, tq, probs, xbar, ctx0 = saved[4 * l: 4 * l + 6]
-                dx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
-                dW_in = torch.empty(3 * D, D, dtype=torch.float32, device=dev)
-                db_in = torch.empty(3 * D, dtype=torch.float32, device=dev)
-                dW_out = torch.empty(D, D, dtype=torch.float32, device=dev)
-                db_out = torch.empty(D, dtype=torch.float32, device=dev)
-                # one workspace for both halves, whichever stream the weight half runs on (the next user of the slot is the
-                # next step's backward pass, behind the end-of-backward join)
-                wsp, wsn = _ws(dev, lib.tt_enc_last_bwd_workspace_bytes(B, H, D, heads), "enc_last")
-                w_used = ctx.folded.get(l, w_in)  # the composed W_in W_o(prev) when the forward ran on the previous layer's context
-                N.check(lib.tt_enc_last_bwd_data(x.data_ptr(), B, H, D, heads, w_used.contiguous().data_ptr(),
-                                                 w_out.contiguous().data_ptr(), d_recent.data_ptr(), 2 * D, tq.data_ptr(),
-                                                 probs.data_ptr(), dx.data_ptr(), wsp, wsn, N.stream()), "tt_enc_last_bwd_data")
-
-                # the weight half ([D, 32] x [32, D] partial products per 32 samples + their reduction) feeds nothing but the
-                # optimiser: third stream (it was the tail of the data kernels: 0.1 ms of the step's critical path)
-                def last_weights(on_side, x=x, q0=q0, xbar=xbar, ctx0=ctx0, dW_in=dW_in, db_in=db_in, dW_out=dW_out, db_out=db_out,
-                                 wsp=wsp, wsn=wsn):
-                    N.check(lib.tt_enc_last_bwd_weights(x.data_ptr(), B, H, D, heads, d_recent.data_ptr(), 2 * D, q0.data_ptr(),
-                                                        xbar.data_ptr(), ctx0.data_ptr(), dW_in.data_ptr(), db_in.data_ptr(),
-                                                        dW_out.data_ptr(), db_out.data_ptr(), wsp, wsn, N.stream()),
-                            "tt_enc_last_bwd_weights")
-
-                # leaves: the Parameters whose gradients the side job writes -- with a composed W_in, dW_in here is the private
-                # G (turned into the two layers' gradients by a tail job on the main stream), so w_in is not among them
-                lw = list(leaf_params[4 * l + 1: 4 * l + 4]) + ([] if l in ctx.folded else [leaf_params[4 * l]])
-                w_aside = False
-                if _EL_WGRAD_SIDE:
-                    w_aside = run_on_side(dev, last_weights, hold=(x, q0, xbar, ctx0, d_out) + ((dW_in,) if l in ctx.folded else ()),
-                                          leaves=lw)
-                else:
-                    last_weights(False)
-                w_done = None
-                if w_aside and l in ctx.folded:  # the tail job below reads G on the main stream
-                    w_done = torch.cuda.Event()
-                    w_done.record(N.aux_stream(dev))
-                if l in ctx.folded:
-                    # dW_in / db_in above are the gradients of (W_eff, b_eff): G and s.  Back to the two layers' own parameters
-                    # (the four small products of a composed boundary, see the full layers below):
-                    #   dW_in = G W_o^T + s (x) b_o     db_in = s     dW_o = W_in^T G     db_o = W_in^T s
-                    w_po, b_po = layer_params[4 * (l - 1) + 2], layer_params[4 * (l - 1) + 3]
-                    G, dW_in = dW_in, torch.empty(3 * D, D, dtype=torch.float32, device=dev)
-                    dW_po = torch.empty(D, D, dtype=torch.float32, device=dev)
-                    db_po = torch.empty(D, dtype=torch.float32, device=dev)
-
-                    def last_folded_weights(on_side, G=G, db_in=db_in, dW_in=dW_in, dW_po=dW_po, db_po=db_po, w_po=w_po, b_po=b_po,
-                                            w_in=w_in):
-                        fold_weight_grads(G, db_in, w_in, w_po, b_po, dW_in, dW_po, db_po)
-
-                    # (issued here on the side stream, these four 10-us products sat behind the persistent attention-backward
-                    # workgroups for 0.45 ms and pushed the streaming weight gradients that much later)
-                    tail_jobs.append((last_folded_weights, w_done))
-                    prev_out_grads = (dW_po, db_po)  # dx is the gradient of the previous layer's CONTEXT
-                grads[4 * l: 4 * l + 4] = [dW_in, db_in, dW_out, db_out]
-                continue
-            x, qkv, ctx_t, lse = saved[4 * l: 4 * l + 4]
-            dW_out = torch.empty(D, D, dtype=torch.float32, device=dev)
-            if prev_out_grads is not None:  # the layer after this one took the context: its backward produced these
-                dW_out, db_out = prev_out_grads
-                d_ctx = dx
-                prev_out_grads = None
-            elif l == L - 1:
-                rows0 = ctx_t.view(B, H * D)[:, :D]
-                _, db_out = gemm_tn_colsum(d_recent, rows0, dW_out)
-                d_ctx = torch.zeros(B * H, D, dtype=torch.float32, device=dev)
-                gemm(N.TT_GEMM_NN, d_recent, w_out, d_ctx.view(B, H * D)[:, :D], B, D, D)
+                dx, grads[4 * l: 4 * l + 4], out_grads, tail_job = _enc_last_bwd(
+                    l, dims, layer_params, leaves, saved[4 * l: 4 * l + 6], w_eff, d_out)
             else:
-                db_out = wgrad(dx, ctx_t, dW_out, "o", l)
-                d_ctx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
-                gemm(N.TT_GEMM_NN, dx, w_out, d_ctx, B * H, D, D)
-            d_qkv = torch.empty(B * H, 3 * D, dtype=torch.float32, device=dev)
-            N.check(lib.tt_attn_bwd(qkv.data_ptr(), ctx_t.data_ptr(), lse.data_ptr(), d_ctx.data_ptr(), B, H, D,
-                                    heads, d_qkv.data_ptr(), N.stream()), "tt_attn_bwd")
-            dW_in = torch.empty(3 * D, D, dtype=torch.float32, device=dev)
-            if l in ctx.folded:
-                # x is the previous layer's context c and qkv = c W_eff^T + b_eff with W_eff = W_in W_o, b_eff = W_in b_o + b_in:
-                #   G = dQKV^T c, s = colsum(dQKV)      dW_in = G W_o^T + s (x) b_o      db_in = s
-                #   dW_o = W_in^T G                      db_o = W_in^T s                  d_c = dQKV W_eff  (the data path)
-                w_po, b_po = layer_params[4 * (l - 1) + 2], layer_params[4 * (l - 1) + 3]
-                w_eff = ctx.folded[l]
-                G = torch.empty(3 * D, D, dtype=torch.float32, device=dev)
-                db_in = torch.empty(3 * D, dtype=torch.float32, device=dev)
-                dW_po = torch.empty(D, D, dtype=torch.float32, device=dev)
-                db_po = torch.empty(D, dtype=torch.float32, device=dev)
-
-                def folded_G(on_side, d_qkv=d_qkv, x=x, G=G, db_in=db_in):
-                    gemm_tn_colsum(d_qkv, x, G, db=db_in, slot="ws_side_i" if on_side else "ws")
-
-                def folded_weights(on_side, G=G, db_in=db_in, dW_in=dW_in, dW_po=dW_po, db_po=db_po, w_po=w_po, b_po=b_po, w_in=w_in):
-                    fold_weight_grads(G, db_in, w_in, w_po, b_po, dW_in, dW_po, db_po)
-
-                # the streaming product G is queued BEFORE the data-path product below (the side stream starts where the main
-                # one stands now); the four small products that turn G into weight gradients wait until the END of this
-                # backward -- in line they sat on the side stream between this layer's G and the next one's, next to the
-                # data path's heaviest kernels, 245 us for 60 us of work, and the side stream finished 250 us after the main one
-                # (held: INPUTS and the private G only -- never db_in, which is returned as in_proj_bias's gradient: a held
-                # output is CLONED by AccumulateGrad on the main stream before the side stream has written it)
-                hold_f = (d_qkv, x, G, w_po, b_po, w_in, w_eff)
-                leaves_f = list(leaf_params[4 * l: 4 * l + 2]) + list(leaf_params[4 * (l - 1) + 2: 4 * (l - 1) + 4])
-                aside = run_on_side(dev, folded_G, hold=hold_f, leaves=leaves_f)
-                g_done = None
-                if aside:  # G is written on the side stream: the tail job (main stream) waits for exactly that
-                    g_done = torch.cuda.Event()
-                    g_done.record(N.aux_stream(dev))
-                tail_jobs.append((folded_weights, g_done))
-                dx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
-                gemm(N.TT_GEMM_NN, d_qkv, w_eff, dx, B * H, D, 3 * D)
-                prev_out_grads = (dW_po, db_po)
-            else:
-                db_in = wgrad(d_qkv, x, dW_in, "i", l)
-                dx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
-                rc = N.TT_E_UNSUPPORTED
-                if l == 0 and not _ENC_GENERIC and w_in.is_contiguous():
-                    rc = lib.tt_hist_dx_pool_bwd(d_qkv.data_ptr(), w_in.data_ptr(), B, H, D, d_pooled.data_ptr(), 2 * D, dx.data_ptr(),
-                                                 N.stream())
-                if rc == 0:
-                    pool_done = True  # the mean pool's backward rode in this product's epilogue (csrc/gemm_ws16.hip, POOL)
-                elif rc == N.TT_E_UNSUPPORTED:  # shape not taken: the product, then a read-modify-write pass over dx
-                    gemm(N.TT_GEMM_NN, d_qkv, w_in, dx, B * H, D, 3 * D)
-                else:
-                    N.check(rc, "tt_hist_dx_pool_bwd")
-            grads[4 * l: 4 * l + 4] = [dW_in, db_in, dW_out, db_out]
-        for fn, g_done in tail_jobs:
-            if g_done is not None:
-                torch.cuda.current_stream().wait_event(g_done)
-            fn(False)
+                dx, grads[4 * l: 4 * l + 4], out_grads, tail_job, pool_done = _enc_layer_bwd(
+                    l, L, dims, layer_params, leaves, saved[4 * l: 4 * l + 4], w_eff, d_out, dx, out_grads)
+            if tail_job is not None:
+                tail_jobs.append(tail_job)
+        for tail_job in tail_jobs:
+            tail_job()
         if dx is None:  # L == 0: slot 0 is row 0 of (x + pe)
-            dx = torch.zeros(B * H, D, dtype=torch.float32, device=dev)
-            dx.view(B, H, D)[:, 0, :].copy_(d_recent)
+            dx = torch.zeros(B * H, D, dtype=torch.float32, device=d_out.device)
+            dx.view(B, H, D)[:, 0, :].copy_(d_out[:, 0, :])
         if not pool_done:
-            N.check(lib.tt_hist_pool_bwd(dx.data_ptr(), B, H, D, d_pooled.data_ptr(), 2 * D, N.stream()),
+            N.check(N.load().tt_hist_pool_bwd(dx.data_ptr(), B, H, D, d_out[:, 1, :].data_ptr(), 2 * D, N.stream()),
                     "tt_hist_pool_bwd")
         d_source = None
         if ctx.needs_input_grad[0]:
