@@ -590,6 +590,46 @@ int tt_enc_last_bwd_weights(const float* x, int64_t B, int64_t H, int64_t D, int
                             int64_t ld_dr, const float* q0, const float* xbar, const float* ctx0, float* dW_in, float* db_in,
                             float* dW_out, float* db_out, void* ws, int64_t ws_bytes, tt_stream_t stream);
 
+/* ---------------------------------------------------------------- K4 with per-sample history lengths
+ * The reference encoder is unmasked because its data is synthetic (ref:src/user_history_encoder.py:80-121,
+ * ref:src/two_tower_with_user_history_encoder.py:105); these are the same pieces under
+ * nn.MultiheadAttention's key_padding_mask = arange(H)[None] >= lengths[:, None].
+ * `lengths` is a device int32 [B]: sample b's LEADING lengths[b] slots are its history, 1 <= lengths[b] <= H; the slots
+ * behind them are padding.  One contract for every call below: sample b is processed as if H were lengths[b], with the
+ * row stride still H; padded rows of the inputs are never read; rows >= lengths[b] of every per-row output (x, ctx, lse,
+ * probs, d_qkv) are WRITTEN AS ZERO -- which is what keeps the library products around these calls (dW = dY^T X,
+ * db = colsum(dY), dx = dY W) exact without touching them.  The value a kernel uses is clamped to [1, H], so a bad length
+ * cannot address outside the sample's rows; only tt_hist_embed_pool_len reports it (*oob_flag = 1).
+ * lengths == NULL: exactly the kernels the call without `_len` launches.
+ *   tt_hist_embed_pool_len  both forms (ids, or ids == NULL: embedded input, whose padded rows may hold anything, NaN and
+ *                           Inf included); pooled[b] = sum_{h < len} row / len; x[b, h >= len] = 0 (no positional row);
+ *                           padded ids are not read.
+ *   tt_hist_pool_bwd_len    dx[b, h < len, :] += d_pooled[b, :] / len, nothing behind them.  The fused
+ *                           tt_hist_dx_pool_bwd has no length form: with lengths a caller runs the product (tt_gemm_f32)
+ *                           and then this call.
+ *   tt_attn_fwd_len / tt_attn_bwd_len  keys and values of padded slots take no part; all implementations honour the lengths
+ *                           (matrix cores for H <= 64, the generic VALU pair otherwise).  The backward routes the shapes of
+ *                           the one-sample-per-workgroup kernel (attention_wg.hip) to the matrix-core kernel when lengths
+ *                           are given.  d_qkv rows of padded slots are zero whatever d_ctx holds there.
+ *   tt_enc_last_fwd_len     probs[b, head, h >= len] = 0; xbar / ctx0 / recent are built from the valid rows only.  The
+ *                           backward halves (tt_enc_last_bwd_data / _weights / tt_enc_last_bwd) need no length form: they
+ *                           see the padding through the saved probs alone, and a zero prob gives a zero score gradient and a
+ *                           zero dx row, PROVIDED x is finite on the padded rows (the calls above write zeros there).
+ * (autograd of the same reference lines with the mask applied.) */
+int tt_hist_embed_pool_len(const float* table, int64_t n_rows, int64_t dim, const int64_t* ids, int64_t B, int64_t H,
+                           const int32_t* lengths /* [B], may be NULL */, const float* pe, float* x, float* pooled,
+                           int64_t ld_pooled, int32_t* oob_flag, tt_stream_t stream);
+int tt_hist_pool_bwd_len(float* dx, int64_t B, int64_t H, int64_t dim, const int32_t* lengths /* [B], may be NULL */,
+                         const float* d_pooled, int64_t ld_pooled, tt_stream_t stream);
+int tt_attn_fwd_len(const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads,
+                    const int32_t* lengths /* [B], may be NULL */, float* ctx, float* lse, tt_stream_t stream);
+int tt_attn_bwd_len(const float* qkv, const float* ctx, const float* lse, const float* d_ctx, int64_t B, int64_t H, int64_t D,
+                    int64_t heads, const int32_t* lengths /* [B], may be NULL */, float* d_qkv, tt_stream_t stream);
+int tt_enc_last_fwd_len(const float* x, int64_t B, int64_t H, int64_t D, int64_t heads,
+                        const int32_t* lengths /* [B], may be NULL */, const float* w_in, const float* b_in, const float* w_out,
+                        const float* b_out, float* recent, int64_t ld_recent, float* q0, float* t, float* probs, float* xbar,
+                        float* ctx0, tt_stream_t stream);
+
 /* ---------------------------------------------------------------- R1 owner routing (row-sharded tables)
  * New design -- the reference has no parallelism.  Tables are split into `world`
  * contiguous blocks of rows_per_rank rows; a rank asks each owner only for the ids that owner holds,

@@ -200,6 +200,12 @@ SIGNATURES = {
                                _vp, _vp, _vp, _i64, _vp]),
     "tt_enc_last_bwd_data": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "tt_enc_last_bwd_weights": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tt_hist_embed_pool_len": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "tt_hist_pool_bwd_len": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "tt_attn_fwd_len": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "tt_attn_bwd_len": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "tt_enc_last_fwd_len": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
     "tt_stream_copy": (_int, [_vp, _vp, _i64, _vp]),
     "tt_mfma_probe_flops": (_i64, [_int, _i32]),
     "tt_mfma_probe": (_int, [_int, _i32, _vp, _i64, _vp]),

@@ -13,14 +13,19 @@
 
 namespace tt {
 
-template <int DHP>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ qkv, int H, int D, int heads, int dh,
-                                                       float* __restrict__ ctx, float* __restrict__ lse) {
+// LEN (the tt_attn_*_len entry points): sample b takes part with its leading lengths[b] rows only (clamped to [1, HS]); the
+// rows behind them are never read and their outputs are written as zero.  HS is the batch's row count = the row stride.
+template <int DHP, bool LEN>
+__global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ qkv, int HS, int D, int heads, int dh,
+                                                       const int32_t* __restrict__ lengths, float* __restrict__ ctx,
+                                                       float* __restrict__ lse) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* Ks = reinterpret_cast<float*>(smem_raw);  // [H][DHP]
-  float* Vs = Ks + (size_t)H * DHP;                // [H][DHP]
+  float* Vs = Ks + (size_t)HS * DHP;               // [H][DHP]
   const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
-  const float* base = qkv + (size_t)b * H * 3 * D + hd * dh;
+  int H = HS;
+  if constexpr (LEN) { const int v = lengths[b]; H = v < 1 ? 1 : (v > HS ? HS : v); }
+  const float* base = qkv + (size_t)b * HS * 3 * D + hd * dh;
   for (int idx = threadIdx.x; idx < H * DHP; idx += blockDim.x) {
     const int j = idx / DHP, d = idx % DHP;
     const bool in = d < dh;
@@ -54,29 +59,39 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
       for (int d = 0; d < DHP; ++d) o[d] = fmaf(p, Vs[j * DHP + d], o[d]);
     }
     const float inv = 1.0f / l;
-    float* out = ctx + ((size_t)b * H + i) * D + hd * dh;
+    float* out = ctx + ((size_t)b * HS + i) * D + hd * dh;
 #pragma unroll
     for (int d = 0; d < DHP; ++d)
       if (d < dh) out[d] = o[d] * inv;
-    lse[((size_t)b * heads + hd) * H + i] = mx + __logf(l);
+    lse[((size_t)b * heads + hd) * HS + i] = mx + __logf(l);
+  }
+  if constexpr (LEN) {
+    for (int i = H + threadIdx.x; i < HS; i += blockDim.x) {
+      float* out = ctx + ((size_t)b * HS + i) * D + hd * dh;
+      for (int d = 0; d < dh; ++d) out[d] = 0.f;
+      lse[((size_t)b * heads + hd) * HS + i] = 0.f;
+    }
   }
 }
 
-template <int DHP>
+template <int DHP, bool LEN>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
                                                        const float* __restrict__ lse, const float* __restrict__ d_ctx,
-                                                       int H, int D, int heads, int dh, float* __restrict__ d_qkv) {
+                                                       int HS, int D, int heads, int dh, const int32_t* __restrict__ lengths,
+                                                       float* __restrict__ d_qkv) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* Qs = reinterpret_cast<float*>(smem_raw);  // [H][DHP]  q * scale
-  float* Ks = Qs + (size_t)H * DHP;
-  float* Vs = Ks + (size_t)H * DHP;
-  float* Gs = Vs + (size_t)H * DHP;  // dO
-  float* Ls = Gs + (size_t)H * DHP;  // [H] row lse
-  float* Ds = Ls + H;                // [H] delta_i = dO_i . O_i
+  float* Ks = Qs + (size_t)HS * DHP;
+  float* Vs = Ks + (size_t)HS * DHP;
+  float* Gs = Vs + (size_t)HS * DHP;  // dO
+  float* Ls = Gs + (size_t)HS * DHP;  // [H] row lse
+  float* Ds = Ls + HS;                // [H] delta_i = dO_i . O_i
   const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
-  const float* base = qkv + (size_t)b * H * 3 * D + hd * dh;
-  const float* cbase = ctx + (size_t)b * H * D + hd * dh;
-  const float* gbase = d_ctx + (size_t)b * H * D + hd * dh;
+  int H = HS;
+  if constexpr (LEN) { const int v = lengths[b]; H = v < 1 ? 1 : (v > HS ? HS : v); }
+  const float* base = qkv + (size_t)b * HS * 3 * D + hd * dh;
+  const float* cbase = ctx + (size_t)b * HS * D + hd * dh;
+  const float* gbase = d_ctx + (size_t)b * HS * D + hd * dh;
   const float scale = 1.0f / sqrtf((float)dh);
   for (int idx = threadIdx.x; idx < H * DHP; idx += blockDim.x) {
     const int j = idx / DHP, d = idx % DHP;
@@ -90,10 +105,18 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
     float dl = 0.f;
     for (int d = 0; d < dh; ++d) dl = fmaf(gbase[(size_t)i * D + d], cbase[(size_t)i * D + d], dl);
     Ds[i] = dl;
-    Ls[i] = lse[((size_t)b * heads + hd) * H + i];
+    Ls[i] = lse[((size_t)b * heads + hd) * HS + i];
   }
   __syncthreads();
-  float* obase = d_qkv + (size_t)b * H * 3 * D + hd * dh;
+  float* obase = d_qkv + (size_t)b * HS * 3 * D + hd * dh;
+  if constexpr (LEN) {  // padded slots: zero gradient rows, whatever d_ctx holds there (it is never read)
+    for (int i = H + threadIdx.x; i < HS; i += blockDim.x)
+      for (int d = 0; d < dh; ++d) {
+        obase[(size_t)i * 3 * D + d] = 0.f;
+        obase[(size_t)i * 3 * D + D + d] = 0.f;
+        obase[(size_t)i * 3 * D + 2 * D + d] = 0.f;
+      }
+  }
   // phase 1: lane = query row i  -> dq_i
   for (int i = threadIdx.x; i < H; i += blockDim.x) {
     float q[DHP], g[DHP], dq[DHP];
@@ -142,9 +165,10 @@ bool attn_bwd_wg_supported(const void* qkv, const void* ctx, const void* d_ctx, 
                            int64_t heads);
 int attn_bwd_wg(const float* qkv, const float* ctx, const float* lse, const float* d_ctx, int64_t B, int64_t H, float* d_qkv,
                 hipStream_t st);
-int attn_fwd_mfma(const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads, float* ctx, float* lse, hipStream_t st);
+int attn_fwd_mfma(const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads, float* ctx, float* lse, hipStream_t st,
+                  const int32_t* lengths = nullptr);
 int attn_bwd_mfma(const float* qkv, const float* lse, const float* d_ctx, int64_t B, int64_t H, int64_t D,
-                  int64_t heads, float* d_qkv, hipStream_t st);
+                  int64_t heads, float* d_qkv, hipStream_t st, const int32_t* lengths = nullptr);
 
 // head widths above 64 (embedding_dim 512 with the history model's 4 heads) take the same kernels with 128 values per
 // lane: they spill past the VGPR file, which makes them slow, not wrong.  Wider heads are refused.
@@ -164,46 +188,74 @@ static int opt_in(K kernel, size_t lds, const char* name) {
 
 using namespace tt;
 
-extern "C" int tt_attn_fwd(const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads, float* ctx,
-                           float* lse, tt_stream_t stream) {
-  if (!qkv || !ctx || !lse) return fail_arg("tt_attn_fwd: null pointer");
-  if (B < 0 || H <= 0 || D <= 0 || heads <= 0 || D % heads != 0) return fail_arg("tt_attn_fwd: sizes");
+// the forward behind tt_attn_fwd (lengths == nullptr) and tt_attn_fwd_len
+static int attn_fwd_any(const char* who, const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads, const int32_t* lengths,
+                        float* ctx, float* lse, tt_stream_t stream) {
+  if (!qkv || !ctx || !lse) { set_error("bad argument: %s: null pointer", who); return TT_E_BADARG; }
+  if (B < 0 || H <= 0 || D <= 0 || heads <= 0 || D % heads != 0) { set_error("bad argument: %s: sizes", who); return TT_E_BADARG; }
   if (B == 0) return 0;
   const int64_t dh = D / heads;
-  if (attn_mfma_supported(qkv, ctx, H, D, dh)) return attn_fwd_mfma(qkv, B, H, D, heads, ctx, lse, S(stream));
+  if (attn_mfma_supported(qkv, ctx, H, D, dh)) return attn_fwd_mfma(qkv, B, H, D, heads, ctx, lse, S(stream), lengths);
   const int dhp = pick_dhp(dh);
-  if (!dhp) { set_error("tt_attn_fwd: head dim %lld > 128 not implemented", (long long)dh); return TT_E_UNSUPPORTED; }
+  if (!dhp) { set_error("%s: head dim %lld > 128 not implemented", who, (long long)dh); return TT_E_UNSUPPORTED; }
   const unsigned threads = (unsigned)(H >= 256 ? 256 : round_up(H, 64));
   const size_t lds = (size_t)2 * H * dhp * sizeof(float);
   const unsigned grid = (unsigned)(B * heads);
   int rc;
-#define TT_FWD(P)                                                                     \
-  if ((rc = opt_in(attn_fwd_kernel<P>, lds, "attn_fwd_kernel"))) return rc;           \
-  attn_fwd_kernel<P><<<grid, threads, lds, S(stream)>>>(qkv, (int)H, (int)D, (int)heads, (int)dh, ctx, lse);
+#define TT_FWD1(P, LEN)                                                                   \
+  if ((rc = opt_in(attn_fwd_kernel<P, LEN>, lds, "attn_fwd_kernel"))) return rc;          \
+  attn_fwd_kernel<P, LEN><<<grid, threads, lds, S(stream)>>>(qkv, (int)H, (int)D, (int)heads, (int)dh, lengths, ctx, lse);
+#define TT_FWD(P) if (lengths) { TT_FWD1(P, true) } else { TT_FWD1(P, false) }
   if (dhp == 4) { TT_FWD(4) } else if (dhp == 16) { TT_FWD(16) } else if (dhp == 32) { TT_FWD(32) } else if (dhp == 64) { TT_FWD(64) } else { TT_FWD(128) }
 #undef TT_FWD
+#undef TT_FWD1
   return check_launch("attn_fwd_kernel");
 }
 
-extern "C" int tt_attn_bwd(const float* qkv, const float* ctx, const float* lse, const float* d_ctx,
-                           int64_t B, int64_t H, int64_t D, int64_t heads, float* d_qkv, tt_stream_t stream) {
-  if (!qkv || !ctx || !lse || !d_ctx || !d_qkv) return fail_arg("tt_attn_bwd: null pointer");
-  if (B < 0 || H <= 0 || D <= 0 || heads <= 0 || D % heads != 0) return fail_arg("tt_attn_bwd: sizes");
+// lengths == nullptr: tt_attn_bwd's own choice among the three kernels.  With lengths the one-sample-per-workgroup kernel
+// (attention_wg.hip) is not taken: its shapes go to the matrix-core kernel, which takes them all.
+static int attn_bwd_any(const char* who, const float* qkv, const float* ctx, const float* lse, const float* d_ctx, int64_t B,
+                        int64_t H, int64_t D, int64_t heads, const int32_t* lengths, float* d_qkv, tt_stream_t stream) {
+  if (!qkv || !ctx || !lse || !d_ctx || !d_qkv) { set_error("bad argument: %s: null pointer", who); return TT_E_BADARG; }
+  if (B < 0 || H <= 0 || D <= 0 || heads <= 0 || D % heads != 0) { set_error("bad argument: %s: sizes", who); return TT_E_BADARG; }
   if (B == 0) return 0;
   const int64_t dh = D / heads;
-  if (attn_bwd_wg_supported(qkv, ctx, d_ctx, d_qkv, H, D, heads)) return attn_bwd_wg(qkv, ctx, lse, d_ctx, B, H, d_qkv, S(stream));
+  if (!lengths && attn_bwd_wg_supported(qkv, ctx, d_ctx, d_qkv, H, D, heads))
+    return attn_bwd_wg(qkv, ctx, lse, d_ctx, B, H, d_qkv, S(stream));
   if (attn_mfma_supported(qkv, d_ctx, H, D, dh) && (reinterpret_cast<uintptr_t>(d_qkv) & 15) == 0)
-    return attn_bwd_mfma(qkv, lse, d_ctx, B, H, D, heads, d_qkv, S(stream));
+    return attn_bwd_mfma(qkv, lse, d_ctx, B, H, D, heads, d_qkv, S(stream), lengths);
   const int dhp = pick_dhp(dh);
-  if (!dhp) { set_error("tt_attn_bwd: head dim %lld > 128 not implemented", (long long)dh); return TT_E_UNSUPPORTED; }
+  if (!dhp) { set_error("%s: head dim %lld > 128 not implemented", who, (long long)dh); return TT_E_UNSUPPORTED; }
   const unsigned threads = (unsigned)(H >= 256 ? 256 : round_up(H, 64));
   const size_t lds = ((size_t)4 * H * dhp + 2 * H) * sizeof(float);
   const unsigned grid = (unsigned)(B * heads);
   int rc;
-#define TT_BWD(P)                                                                     \
-  if ((rc = opt_in(attn_bwd_kernel<P>, lds, "attn_bwd_kernel"))) return rc;           \
-  attn_bwd_kernel<P><<<grid, threads, lds, S(stream)>>>(qkv, ctx, lse, d_ctx, (int)H, (int)D, (int)heads, (int)dh, d_qkv);
+#define TT_BWD1(P, LEN)                                                                   \
+  if ((rc = opt_in(attn_bwd_kernel<P, LEN>, lds, "attn_bwd_kernel"))) return rc;          \
+  attn_bwd_kernel<P, LEN><<<grid, threads, lds, S(stream)>>>(qkv, ctx, lse, d_ctx, (int)H, (int)D, (int)heads, (int)dh, lengths, d_qkv);
+#define TT_BWD(P) if (lengths) { TT_BWD1(P, true) } else { TT_BWD1(P, false) }
   if (dhp == 4) { TT_BWD(4) } else if (dhp == 16) { TT_BWD(16) } else if (dhp == 32) { TT_BWD(32) } else if (dhp == 64) { TT_BWD(64) } else { TT_BWD(128) }
 #undef TT_BWD
+#undef TT_BWD1
   return check_launch("attn_bwd_kernel");
+}
+
+extern "C" int tt_attn_fwd(const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads, float* ctx,
+                           float* lse, tt_stream_t stream) {
+  return attn_fwd_any("tt_attn_fwd", qkv, B, H, D, heads, nullptr, ctx, lse, stream);
+}
+
+extern "C" int tt_attn_bwd(const float* qkv, const float* ctx, const float* lse, const float* d_ctx,
+                           int64_t B, int64_t H, int64_t D, int64_t heads, float* d_qkv, tt_stream_t stream) {
+  return attn_bwd_any("tt_attn_bwd", qkv, ctx, lse, d_ctx, B, H, D, heads, nullptr, d_qkv, stream);
+}
+
+extern "C" int tt_attn_fwd_len(const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads, const int32_t* lengths,
+                               float* ctx, float* lse, tt_stream_t stream) {
+  return attn_fwd_any("tt_attn_fwd_len", qkv, B, H, D, heads, lengths, ctx, lse, stream);
+}
+
+extern "C" int tt_attn_bwd_len(const float* qkv, const float* ctx, const float* lse, const float* d_ctx, int64_t B, int64_t H,
+                               int64_t D, int64_t heads, const int32_t* lengths, float* d_qkv, tt_stream_t stream) {
+  return attn_bwd_any("tt_attn_bwd_len", qkv, ctx, lse, d_ctx, B, H, D, heads, lengths, d_qkv, stream);
 }

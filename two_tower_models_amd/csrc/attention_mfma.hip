@@ -112,9 +112,10 @@ __device__ __forceinline__ void py_accum(f32x16 (&out)[(DH + 31) / 32], const f3
 }
 
 // store an output tile (lane = d, registers = rows x0 + arow) to dst[row*ld + d], rows < H only
-template <int DH>
+// (LEN: rows in [H, Hz) -- the padded slots of a sample shorter than the batch's H -- are written as zero)
+template <int DH, bool LEN = false>
 __device__ __forceinline__ void store_rows(float* __restrict__ dst, int64_t ld, const f32x16 (&t)[(DH + 31) / 32],
-                                           int x0, int H, float scale, int r, int h) {
+                                           int x0, int H, float scale, int r, int h, int Hz = 0) {
   constexpr int TD = (DH + 31) / 32;
 #pragma unroll
   for (int d = 0; d < TD; ++d) {
@@ -124,14 +125,15 @@ __device__ __forceinline__ void store_rows(float* __restrict__ dst, int64_t ld, 
     for (int e = 0; e < 16; ++e) {
       const int row = x0 + arow(e, h);
       if (row < H) dst[(int64_t)row * ld + col] = t[d][e] * scale;
+      else if (LEN && row < Hz) dst[(int64_t)row * ld + col] = 0.f;
     }
   }
 }
 
 // ------------------------------------------------------------------ forward
-template <int DH, int WAVES>
+template <int DH, int WAVES, bool LEN>
 __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 ? 2 : 1)) void attn_fwd_mfma_kernel(const float* __restrict__ qkv, int64_t n_pairs,
-                                                                   int H, int D, int heads,
+                                                                   int HS, int D, int heads, const int32_t* __restrict__ lengths,
                                                                    float* __restrict__ ctx, float* __restrict__ lse) {
   using L = AttnLds<DH>;
   constexpr int TD = (DH + 31) / 32;
@@ -142,7 +144,10 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 ? 2 : 1)) void attn_fwd_mfm
   float* Ks = reinterpret_cast<float*>(smem_raw) + wave * 2 * L::MAT;
   float* Vs = Ks + L::MAT;
   const int64_t b = pair / heads, hd = pair % heads;
-  const float* base = qkv + b * H * 3 * (int64_t)D + hd * DH;
+  // H: the rows of THIS sample that take part (its length, clamped to [1, HS]); HS: the batch's row count = the row stride
+  int H = HS;
+  if constexpr (LEN) { const int v = lengths[b]; H = v < 1 ? 1 : (v > HS ? HS : v); }
+  const float* base = qkv + b * HS * 3 * (int64_t)D + hd * DH;
   const float scale = 1.0f / sqrtf((float)DH);
   // every global load of the pair goes out BEFORE the first wait: K and V rows for the LDS images and the Q fragments
   // of both query tiles.  (Staged one after the other -- K, V, then Q per tile -- the wave sat out four memory round
@@ -173,7 +178,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 ? 2 : 1)) void attn_fwd_mfm
   }
   __builtin_amdgcn_wave_barrier();
 
-  float* out = ctx + b * H * (int64_t)D + hd * DH;
+  float* out = ctx + b * HS * (int64_t)D + hd * DH;
   auto query_tile = [&](int it, const float4 (&qf)[DH / 8]) {  // 32 queries at a time: lane r <-> query it*32 + r
     f32x16 st[2];
     float mx = -3.0e38f;
@@ -209,20 +214,21 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 ? 2 : 1)) void attn_fwd_mfm
       for (int e = 0; e < 16; ++e) st[jt][e] *= inv;
       py_accum<DH>(o, st[jt], Vs, jt * 32, r, h);
     }
-    store_rows<DH>(out, D, o, it * 32, H, 1.f, r, h);
+    store_rows<DH, LEN>(out, D, o, it * 32, H, 1.f, r, h, HS);
     const int i = it * 32 + r;
-    if (h == 0 && i < H) lse[(b * heads + hd) * H + i] = mx + __logf(l);
+    if (h == 0 && i < H) lse[(b * heads + hd) * HS + i] = mx + __logf(l);
+    else if (LEN && h == 0 && i < HS) lse[(b * heads + hd) * HS + i] = 0.f;
   };
   query_tile(0, qf0);
   query_tile(1, qf1);
 }
 
 // ------------------------------------------------------------------ backward
-template <int DH, int WAVES>
+template <int DH, int WAVES, bool LEN>
 __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 ? 2 : 1)) void attn_bwd_mfma_kernel(const float* __restrict__ qkv,
                                                                    const float* __restrict__ lse,
                                                                    const float* __restrict__ d_ctx, int64_t n_pairs,
-                                                                   int H, int D, int heads,
+                                                                   int HS, int D, int heads, const int32_t* __restrict__ lengths,
                                                                    float* __restrict__ d_qkv) {
   using L = AttnLds<DH>;
   constexpr int TD = (DH + 31) / 32;
@@ -236,16 +242,19 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 ? 2 : 1)) void attn_bwd_mfm
   float* Ls = M1 + L::MAT;   // lse per query row (+huge for padding rows -> P = 0)
   float* Ds = Ls + HP;       // delta per query row
   const int64_t b = pair / heads, hd = pair % heads;
-  const float* base = qkv + b * H * 3 * (int64_t)D + hd * DH;
-  const float* gbase = d_ctx + b * H * (int64_t)D + hd * DH;
+  // H: the rows of THIS sample that take part (its length, clamped to [1, HS]); HS: the batch's row count = the row stride
+  int H = HS;
+  if constexpr (LEN) { const int v = lengths[b]; H = v < 1 ? 1 : (v > HS ? HS : v); }
+  const float* base = qkv + b * HS * 3 * (int64_t)D + hd * DH;
+  const float* gbase = d_ctx + b * HS * (int64_t)D + hd * DH;
   const float scale = 1.0f / sqrtf((float)DH);
   float* Ks = M0;
   float* Vs = M1;
   stage<DH>(Ks, base + D, 3 * D, H, 1.f, lane);
   stage<DH>(Vs, base + 2 * D, 3 * D, H, 1.f, lane);
-  Ls[lane] = (lane < H) ? lse[(b * heads + hd) * H + lane] : 3.0e38f;
+  Ls[lane] = (lane < H) ? lse[(b * heads + hd) * HS + lane] : 3.0e38f;
   __builtin_amdgcn_wave_barrier();
-  float* obase = d_qkv + b * H * 3 * (int64_t)D + hd * DH;
+  float* obase = d_qkv + b * HS * 3 * (int64_t)D + hd * DH;
 
   // ---- orientation 1: lane = query i.  dQ and delta.
 #pragma unroll
@@ -281,7 +290,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 ? 2 : 1)) void attn_bwd_mfm
       for (int e = 0; e < 16; ++e) pt[jt][e] *= (dpt[jt][e] - dl);  // dSt[j][i]
       py_accum<DH>(dq, pt[jt], Ks, jt * 32, r, h);
     }
-    store_rows<DH>(obase, 3 * D, dq, it * 32, H, scale, r, h);
+    store_rows<DH, LEN>(obase, 3 * D, dq, it * 32, H, scale, r, h, HS);
   }
   __builtin_amdgcn_wave_barrier();
 
@@ -325,8 +334,8 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 ? 2 : 1)) void attn_bwd_mfm
       py_accum<DH>(dv, p, Gs, it * 32, r, h);
       py_accum<DH>(dk, dp, Qs, it * 32, r, h);  // Qs carries the 1/sqrt(dh) factor
     }
-    store_rows<DH>(obase + 2 * D, 3 * D, dv, jt * 32, H, 1.f, r, h);
-    store_rows<DH>(obase + D, 3 * D, dk, jt * 32, H, 1.f, r, h);
+    store_rows<DH, LEN>(obase + 2 * D, 3 * D, dv, jt * 32, H, 1.f, r, h, HS);
+    store_rows<DH, LEN>(obase + D, 3 * D, dk, jt * 32, H, 1.f, r, h, HS);
   }
 }
 
@@ -338,25 +347,26 @@ static int lds_opt_in(K kernel, size_t lds, const char* name) {
   return 0;
 }
 
-template <int DH>
-static int launch_fwd(const float* qkv, int64_t n_pairs, int H, int D, int heads, float* ctx, float* lse, hipStream_t st) {
+template <int DH, bool LEN>
+static int launch_fwd(const float* qkv, int64_t n_pairs, int H, int D, int heads, const int32_t* lengths, float* ctx, float* lse,
+                      hipStream_t st) {
   constexpr int WAVES = 4;
   const size_t lds = (size_t)WAVES * 2 * AttnLds<DH>::MAT * sizeof(float);
-  int rc = lds_opt_in(attn_fwd_mfma_kernel<DH, WAVES>, lds, "attn_fwd_mfma_kernel");
+  int rc = lds_opt_in(attn_fwd_mfma_kernel<DH, WAVES, LEN>, lds, "attn_fwd_mfma_kernel");
   if (rc) return rc;
   ProfScope prof("attn_fwd_mfma_kernel", st);
-  attn_fwd_mfma_kernel<DH, WAVES><<<(unsigned)ceil_div(n_pairs, WAVES), 64 * WAVES, lds, st>>>(qkv, n_pairs, H, D, heads, ctx, lse);
+  attn_fwd_mfma_kernel<DH, WAVES, LEN><<<(unsigned)ceil_div(n_pairs, WAVES), 64 * WAVES, lds, st>>>(qkv, n_pairs, H, D, heads, lengths, ctx, lse);
   return check_launch("attn_fwd_mfma_kernel");
 }
-template <int DH>
+template <int DH, bool LEN>
 static int launch_bwd(const float* qkv, const float* lse, const float* d_ctx, int64_t n_pairs, int H, int D, int heads,
-                      float* d_qkv, hipStream_t st) {
+                      const int32_t* lengths, float* d_qkv, hipStream_t st) {
   constexpr int WAVES = (DH <= 32) ? 4 : 2;
   const size_t lds = (size_t)WAVES * (2 * AttnLds<DH>::MAT + 2 * HP) * sizeof(float);
-  int rc = lds_opt_in(attn_bwd_mfma_kernel<DH, WAVES>, lds, "attn_bwd_mfma_kernel");
+  int rc = lds_opt_in(attn_bwd_mfma_kernel<DH, WAVES, LEN>, lds, "attn_bwd_mfma_kernel");
   if (rc) return rc;
   ProfScope prof("attn_bwd_mfma_kernel", st);
-  attn_bwd_mfma_kernel<DH, WAVES><<<(unsigned)ceil_div(n_pairs, WAVES), 64 * WAVES, lds, st>>>(qkv, lse, d_ctx, n_pairs, H, D, heads, d_qkv);
+  attn_bwd_mfma_kernel<DH, WAVES, LEN><<<(unsigned)ceil_div(n_pairs, WAVES), 64 * WAVES, lds, st>>>(qkv, lse, d_ctx, n_pairs, H, D, heads, lengths, d_qkv);
   return check_launch("attn_bwd_mfma_kernel");
 }
 
@@ -365,18 +375,28 @@ bool attn_mfma_supported(const void* a, const void* b, int64_t H, int64_t D, int
   return al && H <= HP && (dh == 16 || dh == 32 || dh == 64) && D % 4 == 0;
 }
 
-int attn_fwd_mfma(const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads, float* ctx, float* lse, hipStream_t st) {
+// lengths == nullptr: the kernels every call launched before there were lengths (LEN = false drops every length branch)
+int attn_fwd_mfma(const float* qkv, int64_t B, int64_t H, int64_t D, int64_t heads, float* ctx, float* lse, hipStream_t st,
+                  const int32_t* lengths) {
   const int64_t dh = D / heads, n = B * heads;
-  if (dh == 16) return launch_fwd<16>(qkv, n, (int)H, (int)D, (int)heads, ctx, lse, st);
-  if (dh == 32) return launch_fwd<32>(qkv, n, (int)H, (int)D, (int)heads, ctx, lse, st);
-  return launch_fwd<64>(qkv, n, (int)H, (int)D, (int)heads, ctx, lse, st);
+#define TT_FWD(DH)                                                                                              \
+  return lengths ? launch_fwd<DH, true>(qkv, n, (int)H, (int)D, (int)heads, lengths, ctx, lse, st)              \
+                 : launch_fwd<DH, false>(qkv, n, (int)H, (int)D, (int)heads, nullptr, ctx, lse, st)
+  if (dh == 16) { TT_FWD(16); }
+  if (dh == 32) { TT_FWD(32); }
+  TT_FWD(64);
+#undef TT_FWD
 }
 int attn_bwd_mfma(const float* qkv, const float* lse, const float* d_ctx, int64_t B, int64_t H, int64_t D,
-                  int64_t heads, float* d_qkv, hipStream_t st) {
+                  int64_t heads, float* d_qkv, hipStream_t st, const int32_t* lengths) {
   const int64_t dh = D / heads, n = B * heads;
-  if (dh == 16) return launch_bwd<16>(qkv, lse, d_ctx, n, (int)H, (int)D, (int)heads, d_qkv, st);
-  if (dh == 32) return launch_bwd<32>(qkv, lse, d_ctx, n, (int)H, (int)D, (int)heads, d_qkv, st);
-  return launch_bwd<64>(qkv, lse, d_ctx, n, (int)H, (int)D, (int)heads, d_qkv, st);
+#define TT_BWD(DH)                                                                                              \
+  return lengths ? launch_bwd<DH, true>(qkv, lse, d_ctx, n, (int)H, (int)D, (int)heads, lengths, d_qkv, st)     \
+                 : launch_bwd<DH, false>(qkv, lse, d_ctx, n, (int)H, (int)D, (int)heads, nullptr, d_qkv, st)
+  if (dh == 16) { TT_BWD(16); }
+  if (dh == 32) { TT_BWD(32); }
+  TT_BWD(64);
+#undef TT_BWD
 }
 
 }  // namespace tt

@@ -210,7 +210,12 @@ __global__ __launch_bounds__(256, 1) void enc_last_pre_kernel(const ElArgs p) {
 // ------------------------------------------------------------------ forward: scores, softmax, xbar
 // one workgroup per sample, wave w takes heads w, w+4, ...; lane = history position for the
 // scores, lane = column for the weighted row sum
+// LEN (tt_enc_last_fwd_len): sample b's leading lengths[b] rows (clamped to [1, H]) are its history; the rows behind them are
+// never read, their probs are written as zero and they add nothing to xbar.  Everything downstream of this kernel -- the
+// post kernel and both backward halves -- sees the padding only through those zero probs.
+template <bool LEN>
 __global__ __launch_bounds__(256) void enc_last_main_fwd_kernel(const float* __restrict__ x, int H, int D, int heads,
+                                                                const int32_t* __restrict__ lengths,
                                                                 const float* __restrict__ t, float* __restrict__ probs,
                                                                 float* __restrict__ xbar) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -218,8 +223,10 @@ __global__ __launch_bounds__(256) void enc_last_main_fwd_kernel(const float* __r
   float* Xs = reinterpret_cast<float*>(smem_raw);  // [H][ld]
   float* ts = Xs + H * ld;                         // [heads][D]
   const int64_t b = blockIdx.x;
+  int Hv = H;  // the rows that take part
+  if constexpr (LEN) { const int v = lengths[b]; Hv = v < 1 ? 1 : (v > H ? H : v); }
   const float* xb = x + b * H * D;
-  for (int f = threadIdx.x; f < H * q; f += 256) {
+  for (int f = threadIdx.x; f < Hv * q; f += 256) {
     const int r = f / q, c4 = f % q;
     *reinterpret_cast<float4*>(Xs + r * ld + 4 * c4) = *reinterpret_cast<const float4*>(xb + (int64_t)r * D + 4 * c4);
   }
@@ -230,16 +237,16 @@ __global__ __launch_bounds__(256) void enc_last_main_fwd_kernel(const float* __r
   const float scale = 1.0f / sqrtf((float)(D / heads));
   for (int h = wave; h < heads; h += 4) {
     float sc = -3.0e38f;
-    if (lane < H) sc = scale * row_dot(Xs, ts + h * D, lane, D, 0.f);
+    if (lane < Hv) sc = scale * row_dot(Xs, ts + h * D, lane, D, 0.f);
     const float mx = wave_max(sc);
-    const float e = (lane < H) ? __expf(sc - mx) : 0.f;
+    const float e = (lane < Hv) ? __expf(sc - mx) : 0.f;
     const float l = wave_sum(e);
     const float pj = e / l;
     if (lane < H) probs[(b * heads + h) * H + lane] = pj;
     {  // xbar_h[c] = sum_j p_j X[j][c], columns lane and lane + 64 (D <= 128)
       const int c0 = lane < D ? lane : 0, c1 = lane + 64 < D ? lane + 64 : 0;
       float a0 = 0.f, a1 = 0.f;
-      for (int j = 0; j < H; ++j) {
+      for (int j = 0; j < Hv; ++j) {
         const float pb = __shfl(pj, j, 64);
         a0 = fmaf(pb, Xs[j * ld + c0], a0);
         a1 = fmaf(pb, Xs[j * ld + c1], a1);
@@ -575,9 +582,10 @@ extern "C" int tt_enc_last_supported(int64_t H, int64_t D, int64_t heads) {
           D % heads == 0 && (D / heads) % 4 == 0) ? 1 : 0;
 }
 
-extern "C" int tt_enc_last_fwd(const float* x, int64_t B, int64_t H, int64_t D, int64_t heads, const float* w_in,
-                               const float* b_in, const float* w_out, const float* b_out, float* recent, int64_t ld_recent,
-                               float* q0, float* t, float* probs, float* xbar, float* ctx0, tt_stream_t stream) {
+// tt_enc_last_fwd (lengths == nullptr) and tt_enc_last_fwd_len
+static int enc_last_fwd_any(const float* x, int64_t B, int64_t H, int64_t D, int64_t heads, const int32_t* lengths,
+                            const float* w_in, const float* b_in, const float* w_out, const float* b_out, float* recent,
+                            int64_t ld_recent, float* q0, float* t, float* probs, float* xbar, float* ctx0, tt_stream_t stream) {
   if (!x || !w_in || !b_in || !w_out || !b_out || !recent || !q0 || !t || !probs || !xbar || !ctx0)
     return fail_arg("tt_enc_last_fwd: null pointer");
   if (B < 0 || !tt_enc_last_supported(H, D, heads) || ld_recent < D) {
@@ -600,13 +608,31 @@ extern "C" int tt_enc_last_fwd(const float* x, int64_t B, int64_t H, int64_t D, 
   if ((rc = check_launch("enc_last_pre_kernel"))) return rc;
   {
     const size_t lds = ((size_t)H * (D + 4) + heads * D) * sizeof(float);
-    if ((rc = el_opt_in(enc_last_main_fwd_kernel, lds, "enc_last_main_fwd_kernel"))) return rc;
+    if ((rc = lengths ? el_opt_in(enc_last_main_fwd_kernel<true>, lds, "enc_last_main_fwd_kernel")
+                      : el_opt_in(enc_last_main_fwd_kernel<false>, lds, "enc_last_main_fwd_kernel")))
+      return rc;
     ProfScope prof("enc_last_main_fwd_kernel", st);
-    enc_last_main_fwd_kernel<<<(unsigned)B, 256, lds, st>>>(x, (int)H, (int)D, (int)heads, t, probs, xbar);
+    if (lengths)
+      enc_last_main_fwd_kernel<true><<<(unsigned)B, 256, lds, st>>>(x, (int)H, (int)D, (int)heads, lengths, t, probs, xbar);
+    else
+      enc_last_main_fwd_kernel<false><<<(unsigned)B, 256, lds, st>>>(x, (int)H, (int)D, (int)heads, nullptr, t, probs, xbar);
     if ((rc = check_launch("enc_last_main_fwd_kernel"))) return rc;
   }
   enc_last_post_kernel<<<G, 256, el_small_lds(D), st>>>(a);
   return check_launch("enc_last_post_kernel");
+}
+
+extern "C" int tt_enc_last_fwd(const float* x, int64_t B, int64_t H, int64_t D, int64_t heads, const float* w_in,
+                               const float* b_in, const float* w_out, const float* b_out, float* recent, int64_t ld_recent,
+                               float* q0, float* t, float* probs, float* xbar, float* ctx0, tt_stream_t stream) {
+  return enc_last_fwd_any(x, B, H, D, heads, nullptr, w_in, b_in, w_out, b_out, recent, ld_recent, q0, t, probs, xbar, ctx0, stream);
+}
+
+extern "C" int tt_enc_last_fwd_len(const float* x, int64_t B, int64_t H, int64_t D, int64_t heads, const int32_t* lengths,
+                                   const float* w_in, const float* b_in, const float* w_out, const float* b_out, float* recent,
+                                   int64_t ld_recent, float* q0, float* t, float* probs, float* xbar, float* ctx0,
+                                   tt_stream_t stream) {
+  return enc_last_fwd_any(x, B, H, D, heads, lengths, w_in, b_in, w_out, b_out, recent, ld_recent, q0, t, probs, xbar, ctx0, stream);
 }
 
 extern "C" int64_t tt_enc_last_bwd_workspace_bytes(int64_t B, int64_t H, int64_t D, int64_t heads) {

@@ -76,17 +76,26 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ in, uint16_t* __res
 // History lookup fused with the positional add and the mean pool: every gathered
 // row is read from HBM exactly once.  One workgroup per sample; G = 256/LPR row
 // groups walk h = g, g+G, ...; group partial sums are combined in fixed order.
-template <int VEC, int LPR>
+// LEN (tt_hist_embed_pool_len): sample b's leading lengths[b] slots are its history.  The slots behind them are not read
+// (neither the id nor the row), x is written as ZERO there (no positional row either) and the mean runs over the valid
+// slots.  A length outside [1, H] raises the flag and is clamped into it.
+template <int VEC, int LPR, bool LEN>
 __global__ __launch_bounds__(256) void hist_embed_pool_kernel(
     const float* __restrict__ table, int64_t n_rows, int64_t dimv, const int64_t* __restrict__ ids,
-    int64_t H, const float* __restrict__ pe, float* __restrict__ x, float* __restrict__ pooled,
-    int64_t ld_pooledv, int32_t* oob_flag) {
+    int64_t H, const int32_t* __restrict__ lengths, const float* __restrict__ pe, float* __restrict__ x,
+    float* __restrict__ pooled, int64_t ld_pooledv, int32_t* oob_flag) {
   using V = typename Vec<VEC>::type;
   constexpr int G = 256 / LPR;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   V* part = reinterpret_cast<V*>(smem_raw);  // [G][dimv]
   const int c = threadIdx.x % LPR, g = threadIdx.x / LPR;
   const int64_t b = blockIdx.x;
+  int64_t Hv = H;  // the valid slots
+  if constexpr (LEN) {
+    const int64_t v = lengths[b];
+    if ((v < 1 || v > H) && threadIdx.x == 0) *oob_flag = 1;
+    Hv = v < 1 ? 1 : (v > H ? H : v);
+  }
   const V* pev = reinterpret_cast<const V*>(pe);
   V* xb = reinterpret_cast<V*>(x) + b * H * dimv;
   // U history positions per round: first all ids, then all rows (unconditional loads from clamped
@@ -99,7 +108,7 @@ __global__ __launch_bounds__(256) void hist_embed_pool_kernel(
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t h = h0 + (int64_t)u * G;
-        const int64_t hc = h < H ? h : H - 1;
+        const int64_t hc = h < Hv ? h : Hv - 1;
         id[u] = ids ? ids[b * H + hc] : b * H + hc;
       }
       V v[U];
@@ -112,7 +121,9 @@ __global__ __launch_bounds__(256) void hist_embed_pool_kernel(
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t h = h0 + (int64_t)u * G;
-        if (h < H) {
+        if (LEN && h >= Hv) {
+          if (h < H) xb[h * dimv + k] = Vec<VEC>::zero();
+        } else if (h < H) {
           if (!ok[u]) *oob_flag = 1;
           const V x_in = ok[u] ? v[u] : Vec<VEC>::zero();
           acc = Vec<VEC>::add(acc, x_in);
@@ -124,7 +135,7 @@ __global__ __launch_bounds__(256) void hist_embed_pool_kernel(
   }
   __syncthreads();
   if (g == 0) {
-    const float inv = 1.0f / (float)H;
+    const float inv = 1.0f / (float)Hv;
     for (int64_t k = c; k < dimv; k += LPR) {
       V acc = part[k];
       for (int gg = 1; gg < G; ++gg) acc = Vec<VEC>::add(acc, part[gg * dimv + k]);
@@ -142,6 +153,19 @@ __global__ void hist_pool_bwd_kernel(float* __restrict__ dx, int64_t B, int64_t 
        i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = i / (H * dim), d = i % dim;
     dx[i] += d_pooled[b * ld_pooled + d] * inv;
+  }
+}
+
+// the same with per-sample lengths: dx[b,h,:] += d_pooled[b,:] / len_b for h < len_b (clamped to [1, H]), nothing behind them
+__global__ void hist_pool_bwd_len_kernel(float* __restrict__ dx, int64_t B, int64_t H, int64_t dim,
+                                         const int32_t* __restrict__ lengths, const float* __restrict__ d_pooled,
+                                         int64_t ld_pooled) {
+  const int64_t total = B * H * dim;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / (H * dim), h = (i / dim) % H, d = i % dim;
+    const int64_t v = lengths[b], len = v < 1 ? 1 : (v > H ? H : v);
+    if (h < len) dx[i] += d_pooled[b * ld_pooled + d] * (1.0f / (float)len);
   }
 }
 
@@ -190,9 +214,10 @@ extern "C" int tt_f32_to_bf16(const float* in, uint16_t* out, int64_t n, tt_stre
   return check_launch("f32_to_bf16_kernel");
 }
 
-extern "C" int tt_hist_embed_pool(const float* table, int64_t n_rows, int64_t dim, const int64_t* ids,
-                                  int64_t B, int64_t H, const float* pe, float* x, float* pooled,
-                                  int64_t ld_pooled, int32_t* oob_flag, tt_stream_t stream) {
+// tt_hist_embed_pool (lengths == nullptr) and tt_hist_embed_pool_len
+static int hist_embed_pool_any(const float* table, int64_t n_rows, int64_t dim, const int64_t* ids, int64_t B, int64_t H,
+                               const int32_t* lengths, const float* pe, float* x, float* pooled, int64_t ld_pooled,
+                               int32_t* oob_flag, tt_stream_t stream) {
   if (!table || !x || !pooled || !oob_flag) return fail_arg("tt_hist_embed_pool: null pointer");
   if (dim <= 0 || B < 0 || H <= 0 || ld_pooled < dim || (ids && n_rows <= 0))
     return fail_arg("tt_hist_embed_pool: sizes");
@@ -203,13 +228,31 @@ extern "C" int tt_hist_embed_pool(const float* table, int64_t n_rows, int64_t di
     const int64_t dv = dim / 4;
     const size_t lds = (size_t)(256 / 32) * dv * sizeof(float4);
     if (lds > 64 * 1024) { set_error("tt_hist_embed_pool: dim too large"); return TT_E_UNSUPPORTED; }
-    hist_embed_pool_kernel<4, 32><<<B, 256, lds, S(stream)>>>(table, n_rows, dv, ids, H, pe, x, pooled, ld_pooled / 4, oob_flag);
+    if (lengths)
+      hist_embed_pool_kernel<4, 32, true><<<B, 256, lds, S(stream)>>>(table, n_rows, dv, ids, H, lengths, pe, x, pooled, ld_pooled / 4, oob_flag);
+    else
+      hist_embed_pool_kernel<4, 32, false><<<B, 256, lds, S(stream)>>>(table, n_rows, dv, ids, H, nullptr, pe, x, pooled, ld_pooled / 4, oob_flag);
   } else {
     const size_t lds = (size_t)(256 / 64) * dim * sizeof(float);
     if (lds > 64 * 1024) { set_error("tt_hist_embed_pool: dim too large"); return TT_E_UNSUPPORTED; }
-    hist_embed_pool_kernel<1, 64><<<B, 256, lds, S(stream)>>>(table, n_rows, dim, ids, H, pe, x, pooled, ld_pooled, oob_flag);
+    if (lengths)
+      hist_embed_pool_kernel<1, 64, true><<<B, 256, lds, S(stream)>>>(table, n_rows, dim, ids, H, lengths, pe, x, pooled, ld_pooled, oob_flag);
+    else
+      hist_embed_pool_kernel<1, 64, false><<<B, 256, lds, S(stream)>>>(table, n_rows, dim, ids, H, nullptr, pe, x, pooled, ld_pooled, oob_flag);
   }
   return check_launch("hist_embed_pool_kernel");
+}
+
+extern "C" int tt_hist_embed_pool(const float* table, int64_t n_rows, int64_t dim, const int64_t* ids,
+                                  int64_t B, int64_t H, const float* pe, float* x, float* pooled,
+                                  int64_t ld_pooled, int32_t* oob_flag, tt_stream_t stream) {
+  return hist_embed_pool_any(table, n_rows, dim, ids, B, H, nullptr, pe, x, pooled, ld_pooled, oob_flag, stream);
+}
+
+extern "C" int tt_hist_embed_pool_len(const float* table, int64_t n_rows, int64_t dim, const int64_t* ids, int64_t B, int64_t H,
+                                      const int32_t* lengths, const float* pe, float* x, float* pooled, int64_t ld_pooled,
+                                      int32_t* oob_flag, tt_stream_t stream) {
+  return hist_embed_pool_any(table, n_rows, dim, ids, B, H, lengths, pe, x, pooled, ld_pooled, oob_flag, stream);
 }
 
 namespace tt {
@@ -238,4 +281,16 @@ extern "C" int tt_hist_pool_bwd(float* dx, int64_t B, int64_t H, int64_t dim, co
   const int64_t blocks = ceil_div(total, 256) < 4096 ? ceil_div(total, 256) : 4096;
   hist_pool_bwd_kernel<<<(unsigned)blocks, 256, 0, S(stream)>>>(dx, B, H, dim, d_pooled, ld_pooled);
   return check_launch("hist_pool_bwd_kernel");
+}
+
+extern "C" int tt_hist_pool_bwd_len(float* dx, int64_t B, int64_t H, int64_t dim, const int32_t* lengths, const float* d_pooled,
+                                    int64_t ld_pooled, tt_stream_t stream) {
+  if (!lengths) return tt_hist_pool_bwd(dx, B, H, dim, d_pooled, ld_pooled, stream);
+  if (!dx || !d_pooled) return fail_arg("tt_hist_pool_bwd_len: null pointer");
+  if (B < 0 || H <= 0 || dim <= 0 || ld_pooled < dim) return fail_arg("tt_hist_pool_bwd_len: sizes");
+  if (B == 0) return 0;
+  const int64_t total = B * H * dim;
+  const int64_t blocks = ceil_div(total, 256) < 4096 ? ceil_div(total, 256) : 4096;
+  hist_pool_bwd_len_kernel<<<(unsigned)blocks, 256, 0, S(stream)>>>(dx, B, H, dim, lengths, d_pooled, ld_pooled);
+  return check_launch("hist_pool_bwd_len_kernel");
 }

@@ -1332,9 +1332,13 @@ def fold_weight_grads(G, s, w_in, w_po, b_po, dW_in, dW_po, db_po) -> None:
     gemm(N.TT_GEMM_NN, s.view(1, 3 * D), w_in, db_po.view(1, D), 1, D, 3 * D)
 
 
-def _attn_fwd(qkv, B, H, D, heads):
+def _attn_fwd(qkv, B, H, D, heads, lengths=None):
     ctx_t = torch.empty(B * H, D, dtype=torch.float32, device=qkv.device)
     lse = torch.empty(B, heads, H, dtype=torch.float32, device=qkv.device)
+    if lengths is not None:  # padded slots' keys / values take no part; their ctx rows are written as zero
+        N.check(N.load().tt_attn_fwd_len(qkv.data_ptr(), B, H, D, heads, lengths.data_ptr(), ctx_t.data_ptr(), lse.data_ptr(),
+                                         N.stream()), "tt_attn_fwd_len")
+        return ctx_t, lse
     N.check(N.load().tt_attn_fwd(qkv.data_ptr(), B, H, D, heads, ctx_t.data_ptr(), lse.data_ptr(), N.stream()),
             "tt_attn_fwd")
     return ctx_t, lse
@@ -1369,7 +1373,7 @@ def _compose_aside(dev, layer_params, layers):
     return queued
 
 
-def _enc_layer_fwd(l, L, dims, x, w, b, w_out, b_out, out, sweep_opt):
+def _enc_layer_fwd(l, L, dims, x, w, b, w_out, b_out, out, sweep_opt, lengths=None):
     """A full layer on (w, b), its own in-projection or the composed one -> (the next layer's input, tensors to save)."""
     B, H, D, heads = dims
     qkv = torch.empty(B * H, 3 * D, dtype=torch.float32, device=x.device)
@@ -1383,7 +1387,7 @@ def _enc_layer_fwd(l, L, dims, x, w, b, w_out, b_out, out, sweep_opt):
         started = torch.cuda.Event()
         started.record()
         sweep_opt.release_sweep(after=started)
-    ctx_t, lse = _attn_fwd(qkv, B, H, D, heads)
+    ctx_t, lse = _attn_fwd(qkv, B, H, D, heads, lengths)
     if l + 1 < L and _reads_context(l + 1):
         x_next = ctx_t  # no out-projection here: the next layer takes the context (fold_weights / csrc/encoder_last.hip, PREV)
     elif l + 1 < L:
@@ -1395,7 +1399,7 @@ def _enc_layer_fwd(l, L, dims, x, w, b, w_out, b_out, out, sweep_opt):
     return x_next, [x, qkv, ctx_t, lse]
 
 
-def _enc_last_fwd(dims, x, w, b, w_out, b_out, out):
+def _enc_last_fwd(dims, x, w, b, w_out, b_out, out, lengths=None):
     """The collapsed last layer on (w, b) as for a full layer; writes out[:, 0, :] -> tensors to save."""
     # the last layer is consumed at row 0 only: one query per (sample, head), and its K / V projections fold into two D-wide
     # vectors per (sample, head) -- x is read once, no [B*H, 2D] projection (csrc/encoder_last.hip)
@@ -1406,6 +1410,14 @@ def _enc_last_fwd(dims, x, w, b, w_out, b_out, out):
     probs = torch.empty(B, heads, H, dtype=torch.float32, device=dev)
     xbar = torch.empty(B, heads, D, dtype=torch.float32, device=dev)
     ctx0 = torch.empty(B, D, dtype=torch.float32, device=dev)
+    if lengths is not None:
+        # probs of padded slots are written as zero, which is all the backward halves need (include/tt_hotpath.h)
+        N.check(N.load().tt_enc_last_fwd_len(x.data_ptr(), B, H, D, heads, lengths.data_ptr(), w.contiguous().data_ptr(),
+                                             b.contiguous().data_ptr(), w_out.contiguous().data_ptr(),
+                                             b_out.contiguous().data_ptr(), out.data_ptr(), 2 * D, q0.data_ptr(), tq.data_ptr(),
+                                             probs.data_ptr(), xbar.data_ptr(), ctx0.data_ptr(), N.stream()),
+                "tt_enc_last_fwd_len")
+        return [x, q0, tq, probs, xbar, ctx0]
     N.check(N.load().tt_enc_last_fwd(x.data_ptr(), B, H, D, heads, w.contiguous().data_ptr(), b.contiguous().data_ptr(),
                                      w_out.contiguous().data_ptr(), b_out.contiguous().data_ptr(), out.data_ptr(), 2 * D,
                                      q0.data_ptr(), tq.data_ptr(), probs.data_ptr(), xbar.data_ptr(), ctx0.data_ptr(),
@@ -1484,7 +1496,7 @@ def _enc_last_bwd(l, dims, layer_params, leaves, kept, w_eff, d_out):
     return dx, [dW_in, db_in, dW_out, db_out], below, tail_job
 
 
-def _enc_layer_bwd(l, L, dims, layer_params, leaves, kept, w_eff, d_out, dx, out_grads):
+def _enc_layer_bwd(l, L, dims, layer_params, leaves, kept, w_eff, d_out, dx, out_grads, lengths=None):
     """`dx`: the gradient of the layer's output, or of its CONTEXT if the layer above read that and made `out_grads`.
     -> as _enc_last_bwd, and whether the mean pool's backward is already in dx."""
     B, H, D, heads = dims
@@ -1506,8 +1518,13 @@ def _enc_layer_bwd(l, L, dims, layer_params, leaves, kept, w_eff, d_out, dx, out
         d_ctx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
         gemm(N.TT_GEMM_NN, dx, w_out, d_ctx, B * H, D, D)
     d_qkv = torch.empty(B * H, 3 * D, dtype=torch.float32, device=dev)
-    N.check(lib.tt_attn_bwd(qkv.data_ptr(), ctx_t.data_ptr(), lse.data_ptr(), d_ctx.data_ptr(), B, H, D,
-                            heads, d_qkv.data_ptr(), N.stream()), "tt_attn_bwd")
+    if lengths is not None:
+        # d_qkv rows of padded slots are written as zero: the weight-gradient products and dx = dQKV W below stay as they are
+        N.check(lib.tt_attn_bwd_len(qkv.data_ptr(), ctx_t.data_ptr(), lse.data_ptr(), d_ctx.data_ptr(), B, H, D,
+                                    heads, lengths.data_ptr(), d_qkv.data_ptr(), N.stream()), "tt_attn_bwd_len")
+    else:
+        N.check(lib.tt_attn_bwd(qkv.data_ptr(), ctx_t.data_ptr(), lse.data_ptr(), d_ctx.data_ptr(), B, H, D,
+                                heads, d_qkv.data_ptr(), N.stream()), "tt_attn_bwd")
     dx = torch.empty(B * H, D, dtype=torch.float32, device=dev)
     if w_eff is not None:
         # x is the previous layer's context c and qkv = c W_eff^T + b_eff:  G = dQKV^T c, s = colsum(dQKV) on the side stream,
@@ -1525,7 +1542,9 @@ def _enc_layer_bwd(l, L, dims, layer_params, leaves, kept, w_eff, d_out, dx, out
     dW_in = torch.empty(3 * D, D, dtype=torch.float32, device=dev)
     db_in, _ = _enc_wgrad(d_qkv, x, dW_in, "i", leaves[4 * l: 4 * l + 2])
     rc = N.TT_E_UNSUPPORTED
-    if l == 0 and not _ENC_GENERIC and w_in.is_contiguous():
+    # (with lengths the pool's backward divides by each sample's own length and skips its padded rows: the product alone
+    # here, then tt_hist_pool_bwd_len -- the fused epilogue has no length form)
+    if l == 0 and not _ENC_GENERIC and w_in.is_contiguous() and lengths is None:
         rc = lib.tt_hist_dx_pool_bwd(d_qkv.data_ptr(), w_in.data_ptr(), B, H, D, d_pooled.data_ptr(), 2 * D, dx.data_ptr(),
                                      N.stream())
     if rc == N.TT_E_UNSUPPORTED:  # shape not taken: the product, then a read-modify-write pass over dx (tt_hist_pool_bwd)
@@ -1543,7 +1562,36 @@ class HistoryEncoder(_LookupFunction):
     source = embedding table [N, D] with ids [B, H]   (ids given), or
     source = embedded history [B, H, D]               (ids None).
     Returns [B, 2, D]: slot 0 = row 0 after L attention layers, slot 1 = mean of raw rows.
-    The last layer's out-projection is evaluated for row 0 only (the only row consumed)."""
+    The last layer's out-projection is evaluated for row 0 only (the only row consumed).
+
+    ``apply(..., lengths=t)``: t [B] int32 / int64 on the device, 1 <= t[b] <= H -- sample b's leading t[b] slots are its
+    history, the slots behind them padding (nn.MultiheadAttention's key_padding_mask = arange(H)[None] >= t[:, None] in
+    every layer, the mean over the valid slots, zero gradient for padded rows).  Same layer plan; the `_len` kernels run.
+    A length outside [1, H] raises IndexError at the next poll of the device flag, like an id outside the table."""
+
+    _lengths = [None]  # `lengths` of the apply() in progress (Function.apply takes no keywords)
+
+    @classmethod
+    def apply(cls, *args, lengths: Optional[torch.Tensor] = None):
+        prev = cls._lengths[0]
+        cls._lengths[0] = lengths
+        try:
+            return super().apply(*args)
+        finally:
+            cls._lengths[0] = prev
+
+    @staticmethod
+    def _lengths_i32(lengths, B: int, dev) -> Optional[torch.Tensor]:
+        if lengths is None:
+            return None
+        if not isinstance(lengths, torch.Tensor) or lengths.dtype not in (torch.int64, torch.int32):
+            raise TypeError("history lengths must be an int64 or int32 tensor")
+        if lengths.dim() != 1 or lengths.shape[0] != B:
+            raise ValueError(f"history lengths must have shape [{B}], got {tuple(lengths.shape)}")
+        N.require_device(lengths)
+        if lengths.device != dev:
+            raise RuntimeError(f"tensors on different devices: {dev} vs {lengths.device}")
+        return lengths.to(torch.int32).contiguous()  # once per call; the kernels read int32
 
     @staticmethod
     def forward(ctx, source, ids, pe, heads: int, *layer_params):
@@ -1567,10 +1615,17 @@ class HistoryEncoder(_LookupFunction):
         out = torch.empty(B, 2, D, dtype=torch.float32, device=dev)
         x = torch.empty(B * H, D, dtype=torch.float32, device=dev)
         pooled = out[:, 1, :]
-        N.check(lib.tt_hist_embed_pool(src.data_ptr(), n_rows, D, N.ptr(gather_ids if ids is not None else None), B, H,
-                                       N.ptr(pe), x.data_ptr(),
-                                       pooled.data_ptr(), 2 * D, N.oob.flag(dev).data_ptr(), N.stream()),
-                "tt_hist_embed_pool")
+        lengths = HistoryEncoder._lengths_i32(HistoryEncoder._lengths[0], B, dev)
+        if lengths is not None:
+            # x rows of padded slots are written as zero and never read from the source: every layer below sees finite rows
+            N.check(lib.tt_hist_embed_pool_len(src.data_ptr(), n_rows, D, N.ptr(gather_ids if ids is not None else None), B, H,
+                                               lengths.data_ptr(), N.ptr(pe), x.data_ptr(), pooled.data_ptr(), 2 * D,
+                                               N.oob.flag(dev).data_ptr(), N.stream()), "tt_hist_embed_pool_len")
+        else:
+            N.check(lib.tt_hist_embed_pool(src.data_ptr(), n_rows, D, N.ptr(gather_ids if ids is not None else None), B, H,
+                                           N.ptr(pe), x.data_ptr(),
+                                           pooled.data_ptr(), 2 * D, N.oob.flag(dev).data_ptr(), N.stream()),
+                    "tt_hist_embed_pool")
         sweep_opt = None
         if ids is not None:
             # the step's big gather is queued: a table sweep the optimiser held back for it may start now (optim.py) -- unless
@@ -1608,9 +1663,9 @@ class HistoryEncoder(_LookupFunction):
                     w, b = fold_weights(w, b, *layer_params[4 * l - 2: 4 * l])
                 ctx.composed[l] = (w, b)
             if l == L - 1 and collapsed_last:
-                saved += _enc_last_fwd(dims, x, w, b, w_out, b_out, out)
+                saved += _enc_last_fwd(dims, x, w, b, w_out, b_out, out, lengths)
             else:
-                x, kept = _enc_layer_fwd(l, L, dims, x, w, b, w_out, b_out, out, sweep_opt)
+                x, kept = _enc_layer_fwd(l, L, dims, x, w, b, w_out, b_out, out, sweep_opt, lengths)
                 saved += kept
                 sweep_opt = None
         if L == 0:
@@ -1624,6 +1679,7 @@ class HistoryEncoder(_LookupFunction):
             _side_state["encoder"] = True
         ctx.table = source if ids is not None else None
         ctx.has_ids = ids is not None
+        ctx.lengths = lengths  # int32 [B] or None (no gradient flows to it)
         ctx.save_for_backward(ids, *layer_params, *saved)
         return out
 
@@ -1651,7 +1707,7 @@ class HistoryEncoder(_LookupFunction):
                     l, dims, layer_params, leaves, saved[4 * l: 4 * l + 6], w_eff, d_out)
             else:
                 dx, grads[4 * l: 4 * l + 4], out_grads, tail_job, pool_done = _enc_layer_bwd(
-                    l, L, dims, layer_params, leaves, saved[4 * l: 4 * l + 4], w_eff, d_out, dx, out_grads)
+                    l, L, dims, layer_params, leaves, saved[4 * l: 4 * l + 4], w_eff, d_out, dx, out_grads, ctx.lengths)
             if tail_job is not None:
                 tail_jobs.append(tail_job)
         for tail_job in tail_jobs:
@@ -1659,7 +1715,10 @@ class HistoryEncoder(_LookupFunction):
         if dx is None:  # L == 0: slot 0 is row 0 of (x + pe)
             dx = torch.zeros(B * H, D, dtype=torch.float32, device=d_out.device)
             dx.view(B, H, D)[:, 0, :].copy_(d_out[:, 0, :])
-        if not pool_done:
+        if not pool_done and ctx.lengths is not None:
+            N.check(N.load().tt_hist_pool_bwd_len(dx.data_ptr(), B, H, D, ctx.lengths.data_ptr(), d_out[:, 1, :].data_ptr(),
+                                                  2 * D, N.stream()), "tt_hist_pool_bwd_len")
+        elif not pool_done:
             N.check(N.load().tt_hist_pool_bwd(dx.data_ptr(), B, H, D, d_out[:, 1, :].data_ptr(), 2 * D, N.stream()),
                     "tt_hist_pool_bwd")
         d_source = None

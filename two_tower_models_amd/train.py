@@ -113,12 +113,30 @@ class CandidateSampler:
         return kw
 
 
-def train_one_epoch(model, dataloader, optimizer, device, candidates=None):
+class HistoryLengthSampler:
+    """What ``--min_history_len N`` adds to a batch: per-sample history lengths, uniform in [N, H], drawn on the device from
+    a seeded generator -- the keyword ``user_history_lengths`` of ``train_forward`` (the history ids behind a sample's
+    length stay what the data set drew: valid ids that take no part)."""
+
+    def __init__(self, history_len: int, min_len: int, device: torch.device, seed: int = 9876):
+        if not 1 <= min_len <= history_len:
+            raise SystemExit(f"--min_history_len must be in [1, --user_history_seqlen = {history_len}]")
+        self.lo, self.hi = int(min_len), int(history_len)
+        self.gen = torch.Generator(device=device).manual_seed(seed)
+
+    def __call__(self, user_history: torch.Tensor) -> dict:
+        B, dev = user_history.shape[0], user_history.device
+        return {"user_history_lengths": torch.randint(self.lo, self.hi + 1, (B,), device=dev, generator=self.gen,
+                                                      dtype=torch.int32)}
+
+
+def train_one_epoch(model, dataloader, optimizer, device, candidates=None, history_lengths=None):
     """ref:train/train.py:85-135: forward -> zero_grad -> backward -> step per batch; returns
     the mean loss.  The per-step ``.item()`` of upstream is replaced by one at the end.
     Row-sharded model: the NEXT batch's lookups are announced underneath the current step (parallel.plan_ahead), which
     is what lets the host run ahead of the GPU; purely a scheduling hint.
-    ``candidates`` (a CandidateSampler; default None = the reference's loop): log-Q terms / extra negatives per batch."""
+    ``candidates`` (a CandidateSampler; default None = the reference's loop): log-Q terms / extra negatives per batch.
+    ``history_lengths`` (a HistoryLengthSampler; default None: fixed-length histories): per-sample lengths per batch."""
     model.train()
     total_loss = None
     sharded = parallel.is_sharded(model)
@@ -127,6 +145,8 @@ def train_one_epoch(model, dataloader, optimizer, device, candidates=None):
     while batch is not None:
         user_ids, user_features, user_history, item_ids, item_features, positions, labels = (t.to(device) for t in batch)
         extra = candidates(item_ids) if candidates is not None else {}
+        if history_lengths is not None:
+            extra.update(history_lengths(user_history))
         batch_loss = model.train_forward(user_ids, user_features, user_history, item_ids, item_features,
                                          positions, labels, **extra)
         batch = next(batches, None)
@@ -173,6 +193,11 @@ def main(args):
         raise SystemExit("--num_random_negatives must be >= 0")
     if world > 1 and (logq or n_neg):
         raise SystemExit("--logq / --num_random_negatives are not implemented with --world_size > 1 (row-sharded tables)")
+    min_len = getattr(args, "min_history_len", None)
+    if min_len is not None and world > 1:
+        raise SystemExit("--min_history_len is not implemented with --world_size > 1 (row-sharded tables)")
+    if min_len is not None and args.model == "base":
+        raise SystemExit("--min_history_len needs a model with a history encoder (--model hist or debias)")
     if world > 1:
         device, rank = _init_distributed(world)
     else:
@@ -204,11 +229,14 @@ def main(args):
     optimizer = DenseExactAdam(model.parameters(), lr=args.learning_rate, overlap_sweep="forward",
                                lazy=getattr(args, "lazy_adam", False))
     candidates = CandidateSampler(dataset, logq, n_neg) if (logq or n_neg) else None
+    lengths = HistoryLengthSampler(args.user_history_seqlen, min_len, device) if min_len is not None else None
     stats = []
     for epoch in range(args.num_epochs):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        if candidates is None:
+        if lengths is not None:
+            avg_loss = train_one_epoch(model, dataloader, optimizer, device, candidates=candidates, history_lengths=lengths)
+        elif candidates is None:
             avg_loss = train_one_epoch(model, dataloader, optimizer, device)  # ends with .item(): the device has drained
         else:
             avg_loss = train_one_epoch(model, dataloader, optimizer, device, candidates=candidates)
@@ -278,6 +306,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_random_negatives", type=int, default=0,
                    help="mixed negative sampling: this many uniformly drawn items (random features) per step next to the "
                         "in-batch negatives")
+    p.add_argument("--min_history_len", type=int, default=None,
+                   help="variable-length histories: draw each sample's history length uniformly in [N, --user_history_seqlen] "
+                        "per step and pass it as user_history_lengths (padded slots take no part in the encoder or in any "
+                        "gradient); default: every history is --user_history_seqlen long, as upstream")
     p.add_argument("--lazy_adam", action="store_true",
                    help="value-exact deferred Adam: replay a row's zero-gradient steps when it is next needed")
     return p

@@ -16,6 +16,8 @@ below stays overridable.
 """
 from __future__ import annotations
 
+import contextlib
+import functools
 from typing import List, Optional, Tuple
 
 import torch
@@ -27,6 +29,20 @@ from . import parallel
 from .baseline_mips_module import BaselineMIPSModule
 
 _FEATURE_HIDDEN = 256  # ref:src/two_tower_base_retrieval.py:76-80
+
+
+def takes_history_lengths(fn):
+    """Method decorator: the keyword ``user_history_lengths=None`` behind ``fn``'s own parameters (keyword-only).  When it is
+    given, ``fn`` runs inside ``self._history_lengths(lengths)``; when it is not, ``fn`` is called as it always was.  ``fn``'s
+    own parameter list -- the reference's arguments plus this package's earlier keywords -- stays what introspection reports
+    (functools.wraps); the keyword shows on the wrapper itself (``inspect.signature(m, follow_wrapped=False)``)."""
+    @functools.wraps(fn)
+    def call(self, *args, user_history_lengths: Optional[torch.Tensor] = None, **kwargs):
+        if user_history_lengths is None:
+            return fn(self, *args, **kwargs)
+        with self._history_lengths(user_history_lengths):
+            return fn(self, *args, **kwargs)
+    return call
 
 
 def _feature_mlp(in_features: int, out_features: int) -> nn.Sequential:
@@ -134,9 +150,29 @@ class TwoTowerBaseRetrieval(nn.Module):
         )
         return ops.Linear.apply(item_tower_input, self.item_tower_arch.weight, self.item_tower_arch.bias)
 
+    # ------------------------------------------------------------------ variable-length histories
+    _tt_history_lengths: Optional[torch.Tensor] = None  # set for the duration of ONE train_forward / forward call only
+
+    @contextlib.contextmanager
+    def _history_lengths(self, user_history_lengths: Optional[torch.Tensor]):
+        """Make ``user_history_lengths`` [B] (valid leading slots of each sample's history, 1 <= length <= H) visible to
+        `_history_summary` while the body runs -- the overridable hooks keep their three-argument signatures, a subclass
+        hook that calls super() gets the masked summary -- and to nothing after it returns or raises.  The base model
+        ignores the lengths as it ignores ``user_history``."""
+        if user_history_lengths is not None and self._sharded():
+            raise NotImplementedError("user_history_lengths is not implemented for row-sharded models")
+        prev = self._tt_history_lengths
+        self._tt_history_lengths = user_history_lengths
+        try:
+            yield
+        finally:
+            self._tt_history_lengths = prev
+
     # ------------------------------------------------------------------ inference
+    @takes_history_lengths
     def forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor) -> torch.Tensor:
-        """Top ``num_items`` MIPS row indices per user, [B, num_items] int64 (ref :221-249)."""
+        """Top ``num_items`` MIPS row indices per user, [B, num_items] int64 (ref :221-249).  Keyword
+        ``user_history_lengths`` [B]: see train_forward."""
         # (the result is an index tensor: nothing to differentiate.  Under no_grad the lookups are not recorded for the
         # optimiser's table step -- an inference call between two train steps, with or without the caller's own no_grad,
         # leaves the training bookkeeping alone, and a row-sharded model needs no optimiser to be served)
@@ -333,6 +369,7 @@ class TwoTowerBaseRetrieval(nn.Module):
         if opt is not None:
             opt.begin_step(plan, hold_sweep=hold)
 
+    @takes_history_lengths
     def train_forward(
         self,
         user_id: torch.Tensor,  # [B]
@@ -354,7 +391,14 @@ class TwoTowerBaseRetrieval(nn.Module):
         correction, see compute_training_loss); ``negative_item_id`` / ``negative_item_features`` -- Bn extra items that
         go through the item tower with the batch's own and widen the logits to [B, B + Bn] (mixed negative sampling; the
         positives stay on the leading diagonal, the extra rows get item-tower and table-row gradients like any other
-        item); ``negative_log_q`` -- their log sampling probabilities (needed whenever ``item_log_q`` is given)."""
+        item); ``negative_log_q`` -- their log sampling probabilities (needed whenever ``item_log_q`` is given).
+
+        One more keyword comes from the `takes_history_lengths` decorator:
+        ``user_history_lengths`` (int32 / int64 [B] on the device, default None: fixed-length histories as upstream) --
+        sample b's leading ``user_history_lengths[b]`` slots of ``user_history`` (newest first) are its history,
+        1 <= length <= H; the slots behind them are padding that takes no part in the encoder's attention, its mean
+        pool or any gradient.  Padded ids must still be valid item ids (pad with 0).  A length outside [1, H] raises
+        IndexError like an id outside its table.  The base model ignores it, as it ignores ``user_history``."""
         if any(t is not None for t in (item_log_q, negative_item_id, negative_item_features, negative_log_q)):
             item_id, item_features, item_log_q = self._with_negatives(
                 item_id, item_features, item_log_q, negative_item_id, negative_item_features, negative_log_q)

@@ -34,6 +34,7 @@ import torch.nn.functional as F
 from . import _native as N
 from . import ops
 from .baseline_mips_module import BaselineMIPSModule
+from .two_tower_base_retrieval import takes_history_lengths
 from .two_tower_with_debiasing import TwoTowerWithDebiasing
 
 _WEIGHT_MIN = 1.0e-6  # ref :282-284
@@ -78,6 +79,12 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
         return u, r.view(r.shape[0], self.num_ranker_user_embeddings, u.shape[1])
 
     # ------------------------------------------------------------------ inference
+    def _history_lengths(self, user_history_lengths):
+        """The keyword ``user_history_lengths`` of forward / train_forward is refused: this model's two user-side outputs have
+        no masked reference to be checked against.  (Refused before anything of the model is used.)"""
+        raise NotImplementedError("TwoTowerPlusLightRanker: user_history_lengths is not implemented for the light-ranker model")
+
+    @takes_history_lengths
     def forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor) -> torch.Tensor:
         """Top ``num_items`` of the ``num_mips_items`` MIPS candidates by the light ranker's net value, [B, num_items]
         int64 item ids (ref :131-209)."""
@@ -116,13 +123,15 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
         return torch.gather(idx, dim=1, index=order)
 
     # ------------------------------------------------------------------ training
+    @takes_history_lengths
     def train_forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor,
                       item_id: torch.Tensor, item_features: torch.Tensor, position: torch.Tensor,
                       labels: torch.Tensor, item_log_q=None, negative_item_id=None, negative_item_features=None,
                       negative_log_q=None) -> torch.Tensor:
         """MIPS term + light ranker term (ref :211-340).  No host synchronisation: GraphedTrainStep captures it.
         The log-Q / extra-negative keywords of TwoTowerBaseRetrieval.train_forward are refused: the ranker term scores
-        the impressed item only and has no corrected form here."""
+        the impressed item only and has no corrected form here.  ``user_history_lengths`` is refused as well
+        (`_history_lengths`)."""
         if any(t is not None for t in (item_log_q, negative_item_id, negative_item_features, negative_log_q)):
             raise NotImplementedError("TwoTowerPlusLightRanker.train_forward: item_log_q / negative_* are not implemented "
                                       "for the light-ranker model")

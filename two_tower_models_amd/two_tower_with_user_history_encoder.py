@@ -41,10 +41,14 @@ class TwoTowerWithUserHistoryEncoder(TwoTowerBaseRetrieval):
 
     def _history_summary(self, user_history: torch.Tensor) -> torch.Tensor:
         enc = self.user_history_encoder
+        # the `user_history_lengths` of the train_forward / forward call in progress (TwoTowerBaseRetrieval._history_lengths):
+        # the hooks keep the reference's three-argument signatures, so the lengths do not travel through them
+        lengths = self._tt_history_lengths
         if isinstance(enc, UserHistoryEncoder):
-            summary = enc.encode_ids(self.item_id_embedding_arch.weight, user_history)  # [B, 2, DI]
+            summary = enc.encode_ids(self.item_id_embedding_arch.weight, user_history, lengths)  # [B, 2, DI]
         else:  # a user-supplied encoder module: plain lookup, then the module's own forward
-            summary = enc(ops.EmbeddingLookup.apply(self.item_id_embedding_arch.weight, user_history))
+            embedded = ops.EmbeddingLookup.apply(self.item_id_embedding_arch.weight, user_history)
+            summary = enc(embedded) if lengths is None else enc(embedded, lengths=lengths)
         return summary.view(summary.shape[0], -1)
 
     def compute_user_embedding(

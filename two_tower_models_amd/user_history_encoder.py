@@ -1,8 +1,14 @@
 """UserHistoryEncoder on MI355X (mirror of ref:src/user_history_encoder.py:11-124).
 
-[B, H, DI] history embeddings -> [B, 2, DI]: (row 0 after L stacked, unmasked
+[B, H, DI] history embeddings -> [B, 2, DI]: (row 0 after L stacked
 multi-head self-attention layers with the flipped sinusoid table added,
-mean over H of the raw embeddings).  Parameter names and initialisation match
+mean over H of the raw embeddings).  Unmasked as upstream by default; with
+``lengths`` [B] (1 <= lengths[b] <= H) sample b's leading lengths[b] slots are
+its history and the rest is padding: ``key_padding_mask = arange(H)[None] >=
+lengths[:, None]`` in every layer, the mean over the valid slots only, row h
+still takes row h of the flipped table, and padded slots receive exactly zero
+gradient (padded rows of an embedded input may hold anything; padded ids must
+be valid row ids -- pad with 0).  Parameter names and initialisation match
 ``nn.MultiheadAttention`` inside an ``nn.ModuleList`` exactly
 (``multihead_attn_layers.{i}.in_proj_weight`` ...), including the order of the
 RNG draws, so the reference's seeded known-answer tests reproduce.
@@ -10,6 +16,7 @@ RNG draws, so the reference's seeded known-answer tests reproduce.
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -85,15 +92,22 @@ class UserHistoryEncoder(nn.Module):
     def _pe(self):
         return self.positional_embeddings if self.use_positional_encoding else None
 
-    def forward(self, user_history: torch.Tensor) -> torch.Tensor:
-        """[B, H, DI] (newest item first) -> [B, 2, DI] (ref :80-121)."""
-        return ops.HistoryEncoder.apply(user_history, None, self._pe(), self.num_attention_heads, *self._layer_tensors())
+    def forward(self, user_history: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[B, H, DI] (newest item first) -> [B, 2, DI] (ref :80-121); ``lengths`` [B]: valid leading slots per sample."""
+        if lengths is None:
+            return ops.HistoryEncoder.apply(user_history, None, self._pe(), self.num_attention_heads, *self._layer_tensors())
+        return ops.HistoryEncoder.apply(user_history, None, self._pe(), self.num_attention_heads, *self._layer_tensors(),
+                                        lengths=lengths)
 
-    def encode_ids(self, item_table: torch.Tensor, history_ids: torch.Tensor) -> torch.Tensor:
-        """Same result as ``forward(item_table[history_ids])`` with the lookup fused in:
+    def encode_ids(self, item_table: torch.Tensor, history_ids: torch.Tensor,
+                   lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Same result as ``forward(item_table[history_ids], lengths)`` with the lookup fused in:
         each table row is read from HBM once for both the mean pool and the attention input."""
+        if lengths is None:
+            return ops.HistoryEncoder.apply(item_table, history_ids, self._pe(), self.num_attention_heads,
+                                            *self._layer_tensors())
         return ops.HistoryEncoder.apply(item_table, history_ids, self._pe(), self.num_attention_heads,
-                                        *self._layer_tensors())
+                                        *self._layer_tensors(), lengths=lengths)
 
     def get_output_dim(self) -> int:
         return self.item_id_embedding_dim * 2
