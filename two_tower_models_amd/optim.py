@@ -52,7 +52,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import sys
 import weakref
 from typing import Dict, Iterable, List, Optional, Sequence
 
@@ -60,6 +59,7 @@ import torch
 
 from . import _native as N
 from . import ops
+from .sweep_controller import GroupSweepController, SweepController
 
 
 _RELEASE_AT_LOGITS = True  # a sweep held for the backward logits kernel is released BY that kernel's Function (A/B switch)
@@ -141,10 +141,10 @@ class DenseExactAdam(torch.optim.Optimizer):
         self._ready = False
         self._side_stream: Optional[torch.cuda.Stream] = None
         self.capture_overlap = False  # set by graphs.GraphedTrainStep (multi-stream capture of the overlapped schedule)
-        self._sweep_wgs = 0  # 0 = library default (3 workgroups per CU); lowered by the throttle controller
-        self._tune = None  # events of the step in flight: [begin, sweep start, sweep end, end, level, step number]
-        self._tune_done: List[list] = []  # finished steps whose events may still be pending on the GPU
-        self._tune_state = None  # the sweep-level scan (see _tune_sweep)
+        # how many workgroups the sweep gets (sweep_controller.py): measured on this process's steps, or -- row-sharded
+        # group -- on every rank's, through the group's all-reduce
+        self._sweep_ctl = (GroupSweepController(self._group_reduce(self._sharded[0]))
+                           if self._sharded and self._sharded[0]._tt_shard.world > 1 else SweepController())
         self._plan_stream: Optional[torch.cuda.Stream] = None
         self._plan_done: Optional[torch.cuda.Event] = None
         self._plans_pending = False
@@ -370,7 +370,7 @@ class DenseExactAdam(torch.optim.Optimizer):
         steps = {int(float(st["step"])) for st in self.state.values() if "step" in st}
         if len(steps) > 1:
             raise ValueError("DenseExactAdam needs one common step count for all parameters")
-        self._resume_step = steps.pop() if steps else 0
+        self._resume_step = self._sweep_ctl.resume_step = steps.pop() if steps else 0
         self._begun = None
         self._ready = False  # device-side state is rebuilt around the loaded moments
 
@@ -414,12 +414,13 @@ class DenseExactAdam(torch.optim.Optimizer):
         hyper = self._hyper.data_ptr()
         capturing = torch.cuda.is_current_stream_capturing()  # whole-step hipGraph: no timing events, no controller
         ev_begin = None
-        if not capturing:
+        if capturing:
+            self._sweep_ctl.record = None
+        else:
             self._tune_sweep()
             ev_begin = torch.cuda.Event(enable_timing=True)
             ev_begin.record()
-            if self._tune_done and self._tune_done[-1][5] == self._host_steps and len(self._tune_done[-1]) == 6:
-                self._tune_done[-1].append(ev_begin)  # the previous step's record: its full period ends where this step begins
+            self._sweep_ctl.began(ev_begin, self._host_steps + 1)
         if announced is None:
             N.check(lib.tt_adam_advance(hyper, N.stream()), "tt_adam_advance")
         self._host_steps += 1
@@ -530,8 +531,8 @@ class DenseExactAdam(torch.optim.Optimizer):
                             "tt_adam_tables_sweep")
             self._sweep_done = torch.cuda.Event(enable_timing=not capturing)
             self._sweep_done.record(self._side_stream)
-            if self._tune is not None:
-                self._tune[1], self._tune[2] = ev_s0, self._sweep_done
+            if not capturing:
+                self._sweep_ctl.swept(ev_s0, self._sweep_done)
             if self._sweep_events is not None and ev_s0 is not None and len(self._sweep_events) < 65536:
                 self._sweep_events.append((ev_s0, self._sweep_done))
 
@@ -539,7 +540,6 @@ class DenseExactAdam(torch.optim.Optimizer):
         # gather run BEFORE the sweep starts saturating HBM: next to the sweep it took 281 us instead of 105 (round 4
         # profile), on the critical path.  The gather's Function calls release_sweep() once it is queued; zero_grad() /
         # step() do if nobody did.  The sweep is a third of such a step: starting it 0.1 ms later costs nothing.
-        self._tune = None if capturing else [ev_begin, None, None, None, self._sweep_wgs, self._host_steps]
         self._sweep_done = None
         n_announced = sum(ts.plan.n for ts in begun.values()) if announced is not None else 0
         # ... and a caller whose logits kernels ARE the step (row-sharded tables from W = 4: thin row blocks, W*B negatives
@@ -599,161 +599,33 @@ class DenseExactAdam(torch.optim.Optimizer):
         if pending is not None:
             pending(True, after)
 
-    # The sweep saturates HBM for as long as it lasts, and everything that runs next to it is stretched 2-3x.  When the
-    # sweep IS the step (headline shape: 5.0 of 5.3 ms) that is free; when the forward/backward chain is as long as the
-    # sweep or longer, a thinner sweep (fewer persistent workgroups) that ends with the chain instead of well before it
-    # is faster overall -- C2: 1.27 ms at 768 workgroups, 1.14 at 512, 1.43 at 256; history model: best at 128-256.
-    # The best level depends on the shapes, so it is MEASURED, on the events of steps that have already completed
-    # (queried, never waited on: no host synchronisation is added):
-    #   probe   full width until two steps have been seen; sweep > 0.9 of the step -> keep full width, done
-    #   scan    otherwise the next len(levels) * SCAN_BLOCK steps run the levels one block each, enqueued OPEN LOOP (the
-    #           host may be dozens of steps ahead of the GPU: waiting for each level's verdict before trying the next
-    #           would stretch the scan over hundreds of steps)
-    #   wait    full width until the last scan step's events are in, then the level with the fastest step is kept
-    # and the whole thing repeats every RESCAN_STEPS steps.  Results do not depend on the level: the sweep's chunks
-    # are handed out dynamically either way.
-    _SWEEP_LEVELS = (0, 640, 512, 384, 256, 128)  # workgroups; 0 = library default (3 per CU = 768)
-    _SCAN_BLOCK = 6  # steps per level; the first one of a block overlaps the previous level's tail and is not counted
-    # row-sharded group: every level TWICE (down the list and back up), 16-step blocks, the first 4 steps of a block not
-    # counted, the median of a level's 24 steps kept; the first scan of an optimiser starts after 40 steps.  Pinned levels
-    # at the emulated W = 8 step (tools/bench_emulated_world.py, EMU_FORCE_LEVELS): 4.54 / 4.42 / 4.58 / 4.21 / 4.18 / 4.47
-    # ms for 768 / 512 / 384 / 256 / 192 / 128 workgroups, the same within 0.02 ms at once after every switch.  But the
-    # first ~150 steps of a process run 0.1 - 0.3 ms slower than the steady state and speed up as they go, so a one-way
-    # scan right at the start read its LAST level (128) as the best and kept it: 4.5 instead of 4.2 ms (round 5).
-    _GROUP_SCAN_BLOCK = 16
-    _GROUP_SCAN_SKIP = 4
-    _GROUP_SCAN_DELAY = 40
-    _RESCAN_STEPS = 4000
+    @property
+    def _sweep_wgs(self) -> int:
+        """Workgroups of the sweep launches; 0 = library default (3 per CU)."""
+        return self._sweep_ctl.level
+
+    @_sweep_wgs.setter
+    def _sweep_wgs(self, level: int) -> None:
+        self._sweep_ctl.level = level
+
+    @staticmethod
+    def _group_reduce(table: torch.nn.Parameter):
+        """The row-sharded group's all-reduce as the sweep controller takes it: (values, "min" | "max") -> list of floats."""
+        def reduce(values, op):
+            import torch.distributed as dist
+            from . import collectives
+            t = torch.tensor(values, dtype=torch.float32, device=table.device)
+            collectives.all_reduce_(t, op=getattr(dist.ReduceOp, op.upper()))
+            return [float(v) for v in t.cpu()]
+        return reduce
 
     def sweep_level_note(self) -> str:
         """How the sweep's width was chosen (bench.py prints it)."""
-        ts = self._tune_state
-        if os.environ.get("TT_SWEEP_WGS") is not None:
-            return "fixed by TT_SWEEP_WGS"
-        if ts is None:
-            return "not measured yet"
-        return ts.get("why", ts["phase"])
-
-    # Row-sharded group: the steps of all ranks are synchronised by the collectives, so the best level is a property of
-    # the GROUP, and ranks that locked different levels on local timing noise would drag each other.  Same probe / scan /
-    # decide as below, but every decision is taken at a step number all ranks reach, from the MAX over the ranks of each
-    # level's best step time (two host waits per scan, i.e. per 4000 steps).
-    def _tune_sweep_group(self) -> None:
-        import torch.distributed as dist
-        from . import collectives
-        levels = self._SWEEP_LEVELS
-        step = self._host_steps + 1  # the step about to be enqueued
-        ts = self._tune_state
-        if ts is None:  # (the first probe waits: see _GROUP_SCAN_DELAY)
-            ts = self._tune_state = {"phase": "probe", "t0": step + self._GROUP_SCAN_DELAY, "since": 0}
-
-        def collect():
-            obs = {}
-            for got in self._tune_done:
-                # a step's time = begin to the NEXT step's begin where that is known: what lies between a step's end and
-                # the next one's begin (routing the next batch's lookups) waits for more or less of the sweep's tail
-                # depending on the level -- begin-to-end under-read the slowest level by 0.13 ms and picked it (round 5)
-                last = got[6] if len(got) > 6 else got[3]
-                last.synchronize()
-                if got[5] < ts["t0"] + 4 or got[5] in ts.get("skip", ()):
-                    continue
-                obs.setdefault(got[4], []).append((got[0].elapsed_time(last), got[1].elapsed_time(got[2])))
-            self._tune_done.clear()
-            return obs
-
-        def group(values, op):
-            t = torch.tensor(values, dtype=torch.float32, device=self._hyper.device)
-            collectives.all_reduce_(t, op=op)
-            return [float(v) for v in t.cpu()]
-
-        if ts["phase"] == "probe":
-            self._sweep_wgs = levels[0]
-            if step == ts["t0"] + 8:
-                seen = collect().get(0, [])
-                mine = 1.0 if (len(seen) >= 2 and all(sweep > 0.9 * st for st, sweep in seen[-2:])) else 0.0
-                if group([mine], dist.ReduceOp.MIN)[0] > 0.5:
-                    self._lock_sweep(ts, 0, "the sweep is the step on every rank")
-                else:
-                    plan, skip, nxt = [], set(), step
-                    for lv in levels[1:] + levels[:0:-1]:  # down the levels and back up: a drift over the scan cancels
-                        skip.update(range(nxt, nxt + self._GROUP_SCAN_SKIP))  # a block's first steps are not the level's steady state
-                        plan += [lv] * self._GROUP_SCAN_BLOCK
-                        nxt += self._GROUP_SCAN_BLOCK
-                    skip.add(nxt)
-                    ts.update(phase="scan", plan=plan, skip=skip, scan_start=step)
-        if ts["phase"] == "scan":
-            k = step - ts["scan_start"]
-            self._sweep_wgs = ts["plan"][k] if k < len(ts["plan"]) else levels[0]
-            if k == len(ts["plan"]) + 3:
-                obs = collect()
-                # the MEDIAN step of each level's block (the single-GPU controller keeps the fastest step; here one lucky step
-                # decided between levels 7 % apart in steady state: emulated W = 8, 4.19 vs 4.51 ms, round 5)
-                def median(v):
-                    v = sorted(v)
-                    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
-
-                local = [median([st for st, _ in obs.get(lv, [])]) if len(obs.get(lv, [])) >= 3 else 1.0e9 for lv in levels]
-                worst = group(local, dist.ReduceOp.MAX)
-                best = min(range(len(levels)), key=lambda i: (worst[i], i))
-                self._lock_sweep(ts, levels[best], "group (max over ranks of each level's median step time): "
-                                 + str({(lv or 768): round(v, 3) for lv, v in zip(levels, worst) if v < 1.0e8}))
-        elif ts["phase"] == "locked":
-            self._tune_done.clear()
-            ts["since"] += 1
-            if ts["since"] >= self._RESCAN_STEPS:
-                self._tune_state = {"phase": "probe", "t0": step, "since": 0}
+        return self._sweep_ctl.note()
 
     def _tune_sweep(self) -> None:
-        if os.environ.get("TT_SWEEP_WGS") is not None:
-            return
-        if self._sharded and self._sharded[0]._tt_shard.world > 1:
-            return self._tune_sweep_group()
-        ts = self._tune_state
-        if ts is None:
-            ts = self._tune_state = {"phase": "probe", "obs": {}, "plan": [], "skip": set(), "last": 0, "since": 0}
-        levels = self._SWEEP_LEVELS
-        newest = 0
-        while self._tune_done and self._tune_done[0][2].query() and self._tune_done[0][3].query():
-            got = self._tune_done.pop(0)
-            newest = got[5]
-            if got[5] - int(getattr(self, "_resume_step", 0)) <= 4 or got[5] in ts["skip"]:
-                continue  # the first steps SINCE CONSTRUCTION OR RESUME (allocations, first-use set-up) / the first step of a scan block
-            ts["obs"].setdefault(got[4], []).append((got[0].elapsed_time(got[3]), got[1].elapsed_time(got[2])))
-        if ts["phase"] == "probe":
-            seen = ts["obs"].get(0, [])
-            if len(seen) >= 2:
-                if all(sweep > 0.9 * step for step, sweep in seen[-2:]):
-                    self._lock_sweep(ts, 0, "the sweep is the step")
-                else:
-                    nxt = self._host_steps + 1  # the step about to be enqueued
-                    for lv in levels[1:]:
-                        ts["skip"].add(nxt)
-                        ts["plan"] += [lv] * self._SCAN_BLOCK
-                        nxt += self._SCAN_BLOCK
-                    ts["skip"].add(nxt)  # back to full width: its first step overlaps the thinnest level's tail
-                    ts["last"] = nxt - 1
-                    ts["phase"] = "scan"
-        if ts["phase"] == "scan":
-            if ts["plan"]:
-                self._sweep_wgs = ts["plan"].pop(0)
-            else:
-                self._sweep_wgs = levels[0]
-                ts["phase"] = "wait"
-        elif ts["phase"] == "wait":
-            if newest >= ts["last"]:
-                ms = {lv: min(step for step, _ in o) for lv, o in ts["obs"].items() if len(o) >= 2}
-                self._lock_sweep(ts, min(ms, key=ms.get) if ms else 0, str({(lv or 768): round(v, 3) for lv, v in ms.items()}))
-        elif ts["phase"] == "locked":
-            ts["since"] += 1
-            if ts["since"] >= self._RESCAN_STEPS:
-                self._sweep_wgs = levels[0]
-                ts.update(phase="probe", obs={}, plan=[], skip={self._host_steps + 1}, since=0)
-
-    def _lock_sweep(self, ts: dict, level: int, why: str) -> None:
-        self._sweep_wgs = level
-        ts.update(phase="locked", obs={}, plan=[], skip=set(), since=0, why=f"{level or 768} workgroups: {why}")
-        if os.environ.get("TT_TUNE_DEBUG"):
-            print(f"[tt] sweep level: {level or 768} workgroups ({why})", file=sys.stderr)
+        """Once per overlapped begin outside a capture: the controller chooses the width of the step about to be enqueued."""
+        self._sweep_ctl.tune(self._host_steps + 1)
 
     def _launch_plans(self, side: bool) -> None:
         """Enqueue the deferred row-plan sorts of a forward-mode step (see _begin_overlapped)."""
@@ -900,13 +772,10 @@ class DenseExactAdam(torch.optim.Optimizer):
                     j.side, j.side_bytes = (None, 0) if ts.marked else (ts.side.data_ptr(), ts.side.numel())
                 N.check(lib.tt_adam_tables_finish(jobs, len(self._begun), hyper, N.stream()), "tt_adam_tables_finish")
             self._begun = None
-            if self._tune is not None:
+            if self._sweep_ctl.record is not None:
                 end = torch.cuda.Event(enable_timing=True)
                 end.record()
-                self._tune[3] = end
-                if len(self._tune_done) < 1024:  # never drop a PENDING measurement: when the host runs many steps ahead the
-                    self._tune_done.append(self._tune)  # oldest one is the next to complete (new ones are skipped meanwhile)
-                self._tune = None
+                self._sweep_ctl.ended(end)
         elif self.lazy:
             if self._prefetch_done is not None:  # rows being replayed for a later batch: finish first
                 torch.cuda.current_stream().wait_event(self._prefetch_done)
