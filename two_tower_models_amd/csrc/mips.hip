@@ -1676,7 +1676,12 @@ __global__ __launch_bounds__(256) void mips_split_rows_kernel(const float* __res
 }
 __global__ void mips_unscale_kernel(float* __restrict__ scores, int64_t n, const float* __restrict__ sa, const float* __restrict__ sb) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) scores[i] *= 1.f / (*sa * *sb);  // powers of two: exact
+  if (i >= n) return;
+  // The product of the scales need not be an fp32 number (two matrices with maxima near 2^-50: 2^65 * 2^65), while the
+  // unscaled score is: divide by the mantissas (0.5 * 0.5 for powers of two: exact) and move the exponent in one step.
+  int ea, eb;
+  const float ma = frexpf(*sa, &ea), mb = frexpf(*sb, &eb);
+  scores[i] = ldexpf(scores[i] / (ma * mb), -(ea + eb));
 }
 
 extern "C" int tt_mips_split_rows(const float* X, int64_t rows, int64_t D, uint16_t* out, float* scale, void* ws, int64_t ws_bytes,
