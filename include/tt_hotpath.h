@@ -770,6 +770,26 @@ int tt_gather_rows_bf16(const uint16_t* table, int64_t n_rows, int64_t dim, cons
                         int64_t n_ids, float* out, int64_t ld_out, int32_t* oob_flag,
                         tt_stream_t stream);
 
+/* Exclusion filter for MIPS serving: leave each query's already-seen items out of its top-K.  The model's `forward`
+ * receives the user's history on every call (ref:src/two_tower_base_retrieval.py:221-249) and the reference ignores it.
+ * Under the (score desc, index asc) order the top-K of `corpus \ S`, |S| <= E, is the first K members of the
+ * top-(K + E) list of the whole corpus that are not in S -- so the caller runs tt_mips_topk (or tt_mips_merge) at
+ * n_cand = min(K + E, C) and this call filters, per query b:
+ *   S_b       = { exclude[b, j] : exclude[b, j] >= 0 }   (negative entries are padding, duplicates allowed)
+ *   key(j)    = row_key[idx[b, j]] when row_key is given (corpus row -> item id), else idx[b, j] itself; compared as
+ *               full int64.  A candidate whose idx lies outside [0, C) is dropped and never read through row_key.
+ *   output    = the first K candidates, in input order, whose key is not in S_b: idx and score copied bit for bit.
+ *               Fewer than K survivors: the remaining slots get idx = -1, score = -inf and *short_flag is set to 1
+ *               (never cleared here).  All B*K output slots are written.
+ * No score is recomputed: the result is bit-identical to masking the excluded rows to -inf before the top-K.  Integer
+ * compares and copies only, positions by list order: deterministic.  Needs no workspace.
+ * Sizes: 1 <= K <= n_cand < 2^31, 1 <= E <= 4096, B >= 1, C >= 1; anything else, or a null pointer other than row_key,
+ * returns TT_E_BADARG before anything is enqueued. */
+int tt_mips_exclude(const int64_t* idx /*[B, n_cand]*/, const float* scores /*[B, n_cand]*/, int64_t B, int64_t n_cand,
+                    int64_t K, const int64_t* exclude /*[B, E]*/, int64_t E, const int64_t* row_key /*[C] or NULL*/,
+                    int64_t C, int64_t* idx_out /*[B, K]*/, float* score_out /*[B, K]*/, int32_t* short_flag,
+                    tt_stream_t stream);
+
 /* ---------------------------------------------------------------- light ranker (TwoTowerPlusLightRanker)
  * Per row / candidate: s_n = <R_n, v> (n < NU), p = softmax(s), t = sum_n p_n R_n, m = <u, v>,
  * z = [v | t | s | m] (Z = 2 DI + NU + 1), logits = W z + b with W [T, Z], b [T].  R is [B, NU, DI] with row stride

@@ -235,6 +235,7 @@ SIGNATURES = {
     "tt_mips_split_rows": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "tt_mips_unscale": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "tt_gather_rows_bf16": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "tt_mips_exclude": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tt_light_ranker_supported": (_int, [_i64, _i64, _i64]),
     "tt_light_ranker_head_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "tt_light_ranker_head_fwd": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp,

@@ -12,11 +12,15 @@ Mirrors ref:src/baseline_mips_module.py:10-72 (constructor, ``corpus_size`` /
     module holds only this rank's contiguous row block of the corpus (``corpus_size`` stays the WHOLE corpus' size) and
     the SAME ``forward`` / ``search`` answer for the whole corpus: every rank brings its own B queries and receives its
     own queries' global top-K (int64 GLOBAL row numbers, scores, and -- ``forward`` only -- the [B, K, D] rows fetched
-    from the ranks that own them).  ``model.forward()`` needs no other call.
+    from the ranks that own them).  ``model.forward()`` needs no other call;
+  * ``search`` / ``forward`` take ``exclude`` [B, E]: per query, item keys to leave out of the top-K (a user's seen items).
+    The search runs at ``min(K + E, C)`` and one order-preserving filter kernel (``ops.mips_exclude``) keeps the first K
+    survivors -- bit-identical to masking those rows to -inf before the top-K.  A key is the corpus row number, or
+    ``row_item_id[row]`` when that map is set (``model.index_corpus`` sets it for a catalogue that is not 0..C-1).
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -55,12 +59,17 @@ class BaselineMIPSModule(nn.Module):
         object.__setattr__(self, "_corpus", value)
         object.__setattr__(self, "_split16", None)
         object.__setattr__(self, "_split16_key", None)
+        # ... and the row -> item id map of the previous one: a corpus assigned later is never filtered through a stale map
+        object.__setattr__(self, "row_item_id", None)
 
     def _apply(self, fn, *a, **kw):
         super()._apply(fn, *a, **kw)
+        keys = self.row_item_id
         moved = fn(self.corpus)
         # .to(dtype) requests must not silently change the storage format
         self.corpus = moved if moved.dtype == self.corpus.dtype else moved.to(self.corpus.dtype)
+        if keys is not None:  # the same corpus, moved: its map moves with it
+            self.row_item_id = fn(keys).to(torch.int64)
         return self
 
     def use_bf16_storage(self) -> "BaselineMIPSModule":
@@ -124,9 +133,41 @@ class BaselineMIPSModule(nn.Module):
             self._shard = sh
         return self
 
-    def search(self, query_embedding: torch.Tensor, num_items: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, query_embedding: torch.Tensor, num_items: int,
+               exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(indices int64 [B, K], scores fp32 [B, K]) without gathering the rows.  Row-sharded module: collective -- every
-        rank calls with its own B queries (same B) and gets ITS queries' top-K over the whole corpus, global row numbers."""
+        rank calls with its own B queries (same B) and gets ITS queries' top-K over the whole corpus, global row numbers.
+
+        ``exclude`` (int64 [B, E] on the corpus' device, 1 <= E <= 4096, negative = padding; default None: today's path):
+        query b's top-K among the rows whose key is not in ``exclude[b]`` -- the key of row r is r, or ``row_item_id[r]``
+        when that int64 [C] map is set.  Cost: the search at ``min(K + E, C)`` plus one filter launch.  Fewer than K rows
+        left (possible only when K + E > C, or when ``row_item_id`` repeats an id) raises ``RuntimeError("selected index k
+        out of range")``.  Row-sharded module: the merged list is filtered on global row numbers, no further exchange (E
+        must be the same on every rank, like B); a ``row_item_id`` map is not supported there."""
+        if exclude is None:
+            return self._search(query_embedding, num_items)
+        E = ops.check_exclude(exclude, query_embedding.shape[0])
+        keys = self.row_item_id
+        if self._shard is not None and keys is not None:  # (before any collective)
+            raise NotImplementedError("exclude with a row_item_id map is not implemented for a row-sharded corpus "
+                                      "(keys are global row numbers there)")
+        C = self.corpus_size if self._shard is not None else self.corpus.shape[0]
+        if not (0 < num_items <= C):
+            raise RuntimeError("selected index k out of range")
+        if keys is not None and (keys.dtype != torch.int64 or tuple(keys.shape) != (C,)):
+            raise ValueError(f"row_item_id must be int64 [{C}] (one item id per corpus row)")
+        idx, scores = self._search(query_embedding, min(num_items + E, C))
+        short = torch.zeros(1, dtype=torch.int32, device=idx.device)
+        idx, scores = ops.mips_exclude(idx, scores, num_items, exclude, row_key=keys, num_rows=C, short_flag=short)
+        if self._shard is not None:
+            if num_items + E <= C:
+                return idx, scores  # (row numbers are distinct: at most E of the K + E candidates went)
+            short = parallel.C.all_reduce_(short, op=parallel.dist.ReduceOp.MAX)  # every rank raises, or none
+        if int(short.item()) != 0:  # one 4-byte read: this is inference, and the caller reads the result next
+            raise RuntimeError("selected index k out of range")
+        return idx, scores
+
+    def _search(self, query_embedding: torch.Tensor, num_items: int) -> Tuple[torch.Tensor, torch.Tensor]:
         if self._shard is not None and not (0 < num_items <= self.corpus_size):
             raise RuntimeError("selected index k out of range")  # torch.topk's message, decided on the WHOLE corpus' size
         split = None
@@ -147,9 +188,14 @@ class BaselineMIPSModule(nn.Module):
         self,
         query_embedding: torch.Tensor,  # [B, DI]
         num_items: int,  # (NI)
+        exclude: Optional[torch.Tensor] = None,  # [B, E] item keys to leave out, see search
     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """indices [B, NI] int64, mips_scores [B, NI], embeddings [B, NI, DI] (ref :32-72)."""
-        indices, mips_scores = self.search(query_embedding, num_items)
+        """indices [B, NI] int64, mips_scores [B, NI], embeddings [B, NI, DI] (ref :32-72).  The rows are gathered
+        (row-sharded corpus: fetched) after the exclusion filter."""
+        if exclude is None:
+            indices, mips_scores = self.search(query_embedding, num_items)
+        else:
+            indices, mips_scores = self.search(query_embedding, num_items, exclude)
         if self._shard is not None:  # rows live on their owners: ids out, rows back (the lookups' padded all-to-all)
             return indices, mips_scores, parallel.fetch_rows(self.corpus, self._shard, indices)
         embeddings = ops.gather_corpus_rows(self.corpus, indices)

@@ -1812,6 +1812,60 @@ def mips_merge(scores: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.T
     return out_idx, out_sc
 
 
+MIPS_EXCLUDE_MAX = 4096  # tt_mips_exclude's E limit
+
+
+def check_exclude(exclude: torch.Tensor, B: int) -> int:
+    """Type and shape of an exclusion list (int64 [B, E], 1 <= E <= 4096, negative = padding); returns E.  Raised before
+    any kernel, and before the device check of the other inputs."""
+    if not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int64:
+        raise TypeError("exclude must be an int64 tensor [B, E] of item keys (negative = padding)")
+    if exclude.dim() != 2 or exclude.shape[0] != B:
+        raise ValueError(f"exclude must be [B, E] with B = {B} (one list per query), got {tuple(exclude.shape)}")
+    E = exclude.shape[1]
+    if not (1 <= E <= MIPS_EXCLUDE_MAX):
+        raise ValueError(f"exclude: 1 <= E <= {MIPS_EXCLUDE_MAX} keys per query, got E = {E}")
+    return E
+
+
+def mips_exclude(idx: torch.Tensor, scores: torch.Tensor, k: int, exclude: torch.Tensor,
+                 row_key: Optional[torch.Tensor] = None, num_rows: Optional[int] = None,
+                 short_flag: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per query, the first k of its [B, n_cand] candidates -- in the order given -- whose key is not in its exclusion list
+    `exclude` [B, E] (tt_mips_exclude; csrc/mips_exclude.hip).  The key of a candidate is `row_key[idx]` (int64 [C]: corpus
+    row -> item id) or, without `row_key`, the index itself; candidates outside [0, num_rows) (default: row_key's length, or
+    any non-negative index) are dropped.  Returns (idx [B, k] int64, scores [B, k]), copied bit for bit; where fewer than k
+    survive the tail is -1 / -inf and `short_flag` (int32 [1] on the device, the caller's own) is set to 1."""
+    if idx.dim() != 2 or idx.dtype != torch.int64 or scores.shape != idx.shape or scores.dtype != torch.float32:
+        raise TypeError("mips_exclude: idx int64 [B, n_cand] and scores float32 [B, n_cand]")
+    B, n_cand = idx.shape
+    E = check_exclude(exclude, B)
+    if not (0 < k <= n_cand):
+        raise RuntimeError("selected index k out of range")
+    if row_key is not None and (row_key.dtype != torch.int64 or row_key.dim() != 1):
+        raise TypeError("mips_exclude: row_key must be int64 [C]")
+    dev = N.require_device(idx, scores, exclude, row_key, short_flag)
+    if num_rows is None:
+        num_rows = row_key.shape[0] if row_key is not None else (1 << 63) - 1
+    if row_key is not None and num_rows > row_key.shape[0]:
+        raise ValueError("mips_exclude: num_rows exceeds row_key's length")
+    if short_flag is None:
+        short_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif short_flag.dtype != torch.int32 or short_flag.numel() != 1:
+        raise TypeError("mips_exclude: short_flag must be int32 [1]")
+    idx, scores, exclude = idx.contiguous(), scores.contiguous(), exclude.contiguous()
+    row_key = None if row_key is None else row_key.contiguous()
+    out_idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+    out_sc = torch.empty(B, k, dtype=torch.float32, device=dev)
+    if B == 0:
+        return out_idx, out_sc
+    N.check(N.load().tt_mips_exclude(idx.data_ptr(), scores.data_ptr(), B, n_cand, k, exclude.data_ptr(), E,
+                                     N.ptr(row_key), num_rows,
+                                     out_idx.data_ptr(), out_sc.data_ptr(), short_flag.data_ptr(), N.stream()),
+            "tt_mips_exclude")
+    return out_idx, out_sc
+
+
 def gather_corpus_rows(corpus: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """corpus[idx] -> [B, K, D] fp32 (ref:src/baseline_mips_module.py:63-69)."""
     dev = N.require_device(corpus, idx)

@@ -260,10 +260,17 @@ def main(args):
             model.index_corpus(torch.arange(lo, hi, device=device), feats, bf16=getattr(args, "dtype", "fp32") == "bf16")
             uid, uf, uh = (t.to(device) for t in next(iter(dataloader))[:3])
             model.num_items = min(model.num_items, model.mips_module.corpus_size)
-            top = model(uid, uf, uh)
+            seen_out = bool(getattr(args, "exclude_history", False))
+            if seen_out:  # every user keeps num_items answers even if all of its history would have ranked first
+                model.num_items = max(1, min(model.num_items, model.mips_module.corpus_size - uh.shape[1]))
+                top = model(uid, uf, uh, exclude_history=True)
+            else:
+                top = model(uid, uf, uh)
         say(f"Retrieved top-{top.shape[1]} of {model.mips_module.corpus_size} items for {top.shape[0]} users "
             f"({str(model.mips_module.corpus.dtype).replace('torch.', '')} corpus"
-            + (f", {world} row blocks" if world > 1 else "") + f"); first row: {top[0, :5].tolist()}")
+            + (f", {world} row blocks" if world > 1 else "")
+            + (f", each user's {uh.shape[1]} history items excluded" if seen_out else "")
+            + f"); first row: {top[0, :5].tolist()}")
         stats.append({"retrieved": tuple(top.shape), "corpus_dtype": str(model.mips_module.corpus.dtype)})
     if world > 1:
         import torch.distributed as dist
@@ -310,6 +317,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="variable-length histories: draw each sample's history length uniformly in [N, --user_history_seqlen] "
                         "per step and pass it as user_history_lengths (padded slots take no part in the encoder or in any "
                         "gradient); default: every history is --user_history_seqlen long, as upstream")
+    p.add_argument("--exclude_history", action="store_true",
+                   help="with --retrieve: leave each user's history items out of its top-K (model.forward(..., "
+                        "exclude_history=True): the search runs at K + history length, one filter kernel keeps the first K "
+                        "unseen items); without --retrieve it has no effect")
     p.add_argument("--lazy_adam", action="store_true",
                    help="value-exact deferred Adam: replay a row's zero-gradient steps when it is next needed")
     return p

@@ -170,9 +170,18 @@ class TwoTowerBaseRetrieval(nn.Module):
 
     # ------------------------------------------------------------------ inference
     @takes_history_lengths
-    def forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor) -> torch.Tensor:
+    def forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor, *,
+                exclude_history: bool = False, exclude_item_id: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Top ``num_items`` MIPS row indices per user, [B, num_items] int64 (ref :221-249).  Keyword
-        ``user_history_lengths`` [B]: see train_forward."""
+        ``user_history_lengths`` [B]: see train_forward.
+
+        ``exclude_history=True``: the items of ``user_history`` [B, H] are left out of the user's top-K -- with
+        ``user_history_lengths`` only the valid leading slots (a padded slot's id 0 never excludes item 0).
+        ``exclude_item_id`` (int64 [B, E2], negative = padding): the caller's own list, on top of it or alone.  The ids are
+        ITEM ids: `index_corpus` records which corpus row holds which item (``mips_module.row_item_id``); the returned
+        values stay MIPS row indices, as in the reference.  Cost: the search at K + E plus one filter launch
+        (BaselineMIPSModule.search)."""
+        exclude = self._exclusion_list(user_history, exclude_history, exclude_item_id)
         # (the result is an index tensor: nothing to differentiate.  Under no_grad the lookups are not recorded for the
         # optimiser's table step -- an inference call between two train steps, with or without the caller's own no_grad,
         # leaves the training bookkeeping alone, and a row-sharded model needs no optimiser to be served)
@@ -181,11 +190,43 @@ class TwoTowerBaseRetrieval(nn.Module):
         if type(self.mips_module).forward is BaselineMIPSModule.forward:
             # this package's module: the reference discards the scores and the [B, K, DI] rows (ref :246-248) -- do not
             # gather (row-sharded corpus: do not exchange) half a gigabyte of rows at B = 1024, K = 1000 to drop them
-            top_items, _ = self.mips_module.search(user_embedding, self.num_items)
+            if exclude is None:
+                top_items, _ = self.mips_module.search(user_embedding, self.num_items)
+            else:
+                top_items, _ = self.mips_module.search(user_embedding, self.num_items, exclude)
         else:  # any other mips_module (a subclass, the caller's own): the reference's call, keyword for keyword
             top_items, _, _ = self.mips_module(query_embedding=user_embedding, num_items=self.num_items)
         N.oob.poll(user_embedding.device, blocking=True)
         return top_items
+
+    def _exclusion_list(self, user_history: torch.Tensor, exclude_history: bool,
+                        exclude_item_id: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """int64 [B, E] item ids to leave out of this call's top-K (negative = padding), or None when nothing was asked
+        for.  Everything is checked here, before any kernel or collective of the call."""
+        if not exclude_history and exclude_item_id is None:
+            return None
+        if type(self.mips_module).forward is not BaselineMIPSModule.forward:
+            raise NotImplementedError("exclude_history / exclude_item_id need this package's BaselineMIPSModule (its search "
+                                      f"filters the candidates); got {type(self.mips_module).__name__}")
+        if self.mips_module.is_sharded() and self.mips_module.row_item_id is not None:
+            raise NotImplementedError("exclusion with a row_item_id map is not implemented for a row-sharded corpus")
+        B = user_history.shape[0]
+        parts = []
+        if exclude_history:
+            if user_history.dim() != 2 or user_history.dtype != torch.int64:
+                raise TypeError("exclude_history: user_history must be int64 [B, H]")
+            hist = user_history
+            lengths = self._tt_history_lengths
+            if lengths is not None:  # slots at or beyond the length are padding: id 0 there must not exclude item 0
+                slot = torch.arange(hist.shape[1], device=hist.device).unsqueeze(0)
+                hist = torch.where(slot < lengths.to(hist.device).reshape(B, 1), hist, hist.new_full((), -1))
+            parts.append(hist)
+        if exclude_item_id is not None:
+            ops.check_exclude(exclude_item_id, B)
+            parts.append(exclude_item_id.to(user_history.device))
+        exclude = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        ops.check_exclude(exclude, B)
+        return exclude.contiguous()
 
     # ------------------------------------------------------------------ loss
     @torch.no_grad()
@@ -230,6 +271,16 @@ class TwoTowerBaseRetrieval(nn.Module):
             self.mips_module.set_corpus(out, bf16=bf16, block=True)  # becomes (or stays) row-sharded
         else:
             self.mips_module.set_corpus(out, bf16=bf16)
+        # which item each corpus row holds (what forward's exclusion lists are matched against): nothing to keep when
+        # row r is item r -- a sharded model: global row lo + r of this rank's block --, else the catalogue's ids
+        lo = self.mips_module._shard.lo if sharded else 0
+        rows = torch.arange(lo, lo + item_id.shape[0], device=item_id.device, dtype=item_id.dtype)
+        other = (item_id.reshape(-1) != rows).any().to(torch.int32).reshape(1)  # one device comparison at index time
+        if sharded:  # one decision for the group
+            other = parallel.C.all_reduce_(other, op=parallel.dist.ReduceOp.MAX)
+        # (a row-sharded corpus filters on global row numbers only: with a map set its search REFUSES exclusion, on every
+        # rank alike, rather than match item ids against row numbers)
+        self.mips_module.row_item_id = item_id.detach().to(torch.int64).clone() if int(other.item()) else None
 
     def debias_net_user_value(
         self, net_user_value: torch.Tensor, position: torch.Tensor, user_embedding: torch.Tensor

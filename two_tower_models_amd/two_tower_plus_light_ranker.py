@@ -25,7 +25,7 @@ Differences, all deliberate:
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -85,20 +85,28 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
         raise NotImplementedError("TwoTowerPlusLightRanker: user_history_lengths is not implemented for the light-ranker model")
 
     @takes_history_lengths
-    def forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor) -> torch.Tensor:
+    def forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor, *,
+                exclude_history: bool = False, exclude_item_id: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Top ``num_items`` of the ``num_mips_items`` MIPS candidates by the light ranker's net value, [B, num_items]
-        int64 item ids (ref :131-209)."""
+        int64 item ids (ref :131-209).  ``exclude_history`` / ``exclude_item_id``: as TwoTowerBaseRetrieval.forward -- the
+        ``num_mips_items`` candidates handed to the rerank already leave those items out; the rerank itself is unchanged."""
         self._check_unsharded("forward")
         if self.num_items > self.num_mips_items:
             raise RuntimeError("selected index k out of range")  # torch.topk's message (ref :202-204)
+        exclude = self._exclusion_list(user_history, exclude_history, exclude_item_id)
         with torch.no_grad():
             u, R = self.compute_user_embedding(user_id, user_features, user_history)
             mips = self.mips_module
             corpus = rows = None
             if type(mips).forward is BaselineMIPSModule.forward and not mips.is_sharded():
                 # this package's module: ids and scores only, the rerank reads the rows from the corpus itself
-                idx, scores = mips.search(u, self.num_mips_items)
+                if exclude is None:
+                    idx, scores = mips.search(u, self.num_mips_items)
+                else:
+                    idx, scores = mips.search(u, self.num_mips_items, exclude)
                 corpus = mips.corpus
+            elif exclude is not None:  # (this package's module with a row-sharded corpus: it filters before it fetches)
+                idx, scores, rows = mips(query_embedding=u, num_items=self.num_mips_items, exclude=exclude)
             else:  # any other mips_module: the reference's call, keyword for keyword (ref :153-155)
                 idx, scores, rows = mips(query_embedding=u, num_items=self.num_mips_items)
             lin = self.light_ranker
