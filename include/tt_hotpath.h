@@ -158,7 +158,8 @@ int tt_tower_bwd_weights(const tt_tower_wgrad_side* sides /*host*/, int32_t n_si
 /* ---------------------------------------------------------------- K5 in-batch softmax CE
  * Forward: S = U I^T is never written to memory.
  *   row_lse[i] = log2 sum_j 2^(S[i,j] log2 e)   (= logsumexp_j S[i,j] / ln 2; opaque to the caller,
- *                                                 saved for tt_inbatch_ce_bwd which works in base 2)
+ *                                                 saved for tt_inbatch_ce_bwd which works in base 2).  The unit depends
+ *                                                 on the width: log2 domain for D <= 128, natural-log units for D > 128.
  *   row_ce[i]  = logsumexp_j S[i,j] - S[i, i+diag_offset]
  * replaces torch.matmul + F.cross_entropy(reduction="none") at
  * ref:src/two_tower_base_retrieval.py:287,301-312.  U is [M,D], I is [N,D];

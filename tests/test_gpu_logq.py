@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 import fixture_gen as fg
+from ce_ref import signed_bias, zipf_bias  # the two terms (shared with the float64 CE reference's cases)
 from oracle import cpu_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -41,18 +42,6 @@ def g(shape, seed):
     return torch.from_numpy(fg.gaussianish(shape, seed))
 
 
-def zipf_bias(n, seed=71):
-    """-log q of a Zipf(1.0) popularity over 10^6 items at n seeded ids."""
-    ids = torch.from_numpy(fg.uniform_ids((n,), 10 ** 6, seed).astype(np.int64))
-    harmonic = float(np.sum(1.0 / np.arange(1, 10 ** 6 + 1, dtype=np.float64)))
-    return (torch.log(ids.double() + 1.0) + math.log(harmonic)).float()
-
-
-def signed_bias(n, seed=72):
-    b = g((n,), seed)
-    return b * (30.0 / float(b.abs().max()))
-
-
 def oracle_rows(U, I, b, off):
     scores = R.inbatch_logits(U, I) + b[None, :]
     return F.cross_entropy(scores, torch.arange(U.shape[0]) + off, reduction="none")
@@ -69,54 +58,95 @@ def close_grad(got, want, rtol=1e-4):
     return torch.allclose(got.cpu().to(want.dtype), want, atol=1e-5 * float(want.abs().max()) + 1e-9, rtol=rtol)
 
 
-def abi_fwd(T, U, I, off, bias, form="plain", labels=None, uvw=None):
-    """tt_inbatch_ce_bias_fwd in one of its forms; bias None = NULL.  Returns a dict of its outputs."""
+def _ld(t):
+    """Leading dimension of a row-major (possibly row-strided) [rows, D] view."""
+    return max(t.stride(0), t.shape[1])
+
+
+def abi_workspace(T, M, Nn, D):
+    """The scratch tensor the abi_* helpers hand to the library (at least the biased calls' size)."""
+    ops, N = T
+    return N.scratch.get(torch.device(DEV), N.load().tt_inbatch_ce_bias_workspace_bytes(M, Nn, D), "logq_test")
+
+
+def abi_fwd(T, U, I, off, bias, form="plain", labels=None, uvw=None, *, entry="bias", du_unit=None, logits=None, fill=None):
+    """tt_inbatch_ce_bias_fwd in one of its forms; bias None = NULL.  Returns a dict of its outputs.
+    U, I (and du_unit, if given: a preallocated output view) may be row-strided views: their row stride is the leading
+    dimension passed.  entry="plain": the calls without the term argument (tt_inbatch_ce_fwd, _fwd_du, _fwd_du_keep,
+    _fwd_du_loss) instead.  logits: a preallocated buffer of at least tt_inbatch_ce_logits_bytes.  fill: the value the
+    outputs allocated here hold before the call (default: uninitialised)."""
     ops, N = T
     lib = N.load()
     M, D = U.shape
     Nn = I.shape[0]
-    e = lambda *shape: torch.empty(*shape, device=DEV)
+    e = lambda *shape: torch.empty(*shape, device=DEV) if fill is None else torch.empty(*shape, device=DEV).fill_(fill)
     out = dict(lse=e(M), ce=e(M))
     wsp, wsn = ops._ws(torch.device(DEV), lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D), "logq_test")
-    du = logits = None
+    du = None
     zn = 0
     tail = (None, 1, None, None, None, None)
     if form != "plain":
-        du = out["du_unit"] = e(M, D)
+        du = out["du_unit"] = e(M, D) if du_unit is None else du_unit
     if form == "keep":
         zn = lib.tt_inbatch_ce_logits_bytes(M, Nn)
-        logits = out["logits"] = torch.empty(zn, dtype=torch.uint8, device=DEV)
+        logits = out["logits"] = torch.empty(zn, dtype=torch.uint8, device=DEV) if logits is None else logits
+    else:
+        logits = None
     if form == "loss":
         out.update(w=e(M), coef=e(M), loss=e(()))
         tail = (N.ptr(labels), labels.shape[1] if labels is not None else 1, uvw.data_ptr(), out["w"].data_ptr(),
                 out["coef"].data_ptr(), out["loss"].data_ptr())
-    N.check(lib.tt_inbatch_ce_bias_fwd(U.data_ptr(), D, I.data_ptr(), D, M, Nn, D, off, N.ptr(bias), out["lse"].data_ptr(),
-                                       out["ce"].data_ptr(), N.ptr(du), D, N.ptr(logits), zn, *tail, wsp, wsn, N.stream()),
-            "tt_inbatch_ce_bias_fwd")
+    ld_du = _ld(du) if du is not None else D
+    head = (U.data_ptr(), _ld(U), I.data_ptr(), _ld(I), M, Nn, D, off)
+    stats = (out["lse"].data_ptr(), out["ce"].data_ptr())
+    if entry == "bias":
+        N.check(lib.tt_inbatch_ce_bias_fwd(*head, N.ptr(bias), *stats, N.ptr(du), ld_du, N.ptr(logits), zn, *tail, wsp, wsn,
+                                           N.stream()), "tt_inbatch_ce_bias_fwd")
+        return out
+    assert entry == "plain" and bias is None
+    if form == "plain":
+        N.check(lib.tt_inbatch_ce_fwd(*head, *stats, wsp, wsn, N.stream()), "tt_inbatch_ce_fwd")
+    elif form == "du":
+        N.check(lib.tt_inbatch_ce_fwd_du(*head, *stats, du.data_ptr(), ld_du, wsp, wsn, N.stream()), "tt_inbatch_ce_fwd_du")
+    elif form == "keep":
+        N.check(lib.tt_inbatch_ce_fwd_du_keep(*head, *stats, du.data_ptr(), ld_du, logits.data_ptr(), zn, wsp, wsn, N.stream()),
+                "tt_inbatch_ce_fwd_du_keep")
+    else:
+        N.check(lib.tt_inbatch_ce_fwd_du_loss(*head, tail[0], tail[1], tail[2], *stats, du.data_ptr(), ld_du, *tail[3:], wsp, wsn,
+                                              N.stream()), "tt_inbatch_ce_fwd_du_loss")
     return out
 
 
-def abi_bwd(T, U, I, off, bias, lse, coef, with_du=True):
+def abi_bwd(T, U, I, off, bias, lse, coef, with_du=True, *, entry="bias", dU=None, dI=None):
+    """tt_inbatch_ce_bias_bwd (entry="plain": tt_inbatch_ce_bwd); U, I and the preallocated dU / dI may be row-strided."""
     ops, N = T
     lib = N.load()
     M, D = U.shape
     Nn = I.shape[0]
     wsp, wsn = ops._ws(torch.device(DEV), lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D), "logq_test")
-    dU = torch.empty(M, D, device=DEV) if with_du else None
-    dI = torch.empty(Nn, D, device=DEV)
-    N.check(lib.tt_inbatch_ce_bias_bwd(U.data_ptr(), D, I.data_ptr(), D, M, Nn, D, off, N.ptr(bias), lse.data_ptr(), coef.data_ptr(),
-                                       N.ptr(dU), D, dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bias_bwd")
+    if with_du and dU is None:
+        dU = torch.empty(M, D, device=DEV)
+    dU = dU if with_du else None
+    dI = torch.empty(Nn, D, device=DEV) if dI is None else dI
+    head = (U.data_ptr(), _ld(U), I.data_ptr(), _ld(I), M, Nn, D, off)
+    rest = (lse.data_ptr(), coef.data_ptr(), N.ptr(dU), _ld(dU) if dU is not None else D, dI.data_ptr(), _ld(dI), wsp, wsn, N.stream())
+    if entry == "bias":
+        N.check(lib.tt_inbatch_ce_bias_bwd(*head, N.ptr(bias), *rest), "tt_inbatch_ce_bias_bwd")
+    else:
+        assert entry == "plain" and bias is None
+        N.check(lib.tt_inbatch_ce_bwd(*head, *rest), "tt_inbatch_ce_bwd")
     return dU, dI
 
 
-def abi_bwd_kept(T, U, Nn, off, lse, coef, logits):
+def abi_bwd_kept(T, U, Nn, off, lse, coef, logits, *, dI=None):
     ops, N = T
     lib = N.load()
     M, D = U.shape
     wsp, wsn = ops._ws(torch.device(DEV), lib.tt_inbatch_ce_workspace_bytes(M, Nn, D), "logq_test")
-    dI = torch.empty(Nn, D, device=DEV)
-    N.check(lib.tt_inbatch_ce_bwd_kept(U.data_ptr(), D, M, Nn, D, off, lse.data_ptr(), coef.data_ptr(), logits.data_ptr(),
-                                       logits.numel(), dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bwd_kept")
+    dI = torch.empty(Nn, D, device=DEV) if dI is None else dI
+    N.check(lib.tt_inbatch_ce_bwd_kept(U.data_ptr(), _ld(U), M, Nn, D, off, lse.data_ptr(), coef.data_ptr(), logits.data_ptr(),
+                                       lib.tt_inbatch_ce_logits_bytes(M, Nn), dI.data_ptr(), _ld(dI), wsp, wsn, N.stream()),
+            "tt_inbatch_ce_bwd_kept")
     return dI
 
 
