@@ -88,9 +88,11 @@ def test_gemm_tn_with_fused_column_sum(T, rows, n_out, k_in):
 @pytest.mark.parametrize("rows,n_out", [(204800, 384), (50001, 384), (16400, 384), (8195, 384), (8192, 384),
                                         (50001, 256), (16400, 128)])
 def test_gemm_tn_streaming_path(T, rows, n_out):
-    """K >= 8192 rows, N = 128, M = 384 (M = 128 / 256 with TT_GEMM_TN_STREAM_ALL=1, else the tiled kernel):
-    the register-resident streaming TN kernel (gemm_tn_stream.hip) -- ragged and odd row counts, strided
-    operands, accumulate, determinism."""
+    """K >= 8192 rows, N = 128: M = 384 takes the register-resident streaming TN kernel (gemm_tn_stream.hip) -- ragged
+    and odd row counts, strided operands, accumulate, determinism.  The M = 256 and M = 128 cases run the TILED split-K
+    kernel here: they stream only under TT_GEMM_TN_STREAM_ALL=1, which the library reads once per process and this
+    process never sets (test_gpu_gemm_reference.py runs them in a child process with the variable set, and asserts which
+    kernel ran in both)."""
     ops, N = T
     dy_full, x_full = g((rows, n_out + 8), 311), g((rows, 132), 312)
     dy, x = dy_full[:, 4:4 + n_out], x_full[:, :128]
@@ -889,7 +891,7 @@ def test_gemm_weights_stationary_path(T, layout, M, Nn, K):
     ref = A.double() @ (W.t() if layout == 0 else W).double() + bias.double()
     Ad, Wd = A.to(DEV), W.to(DEV)
     big = torch.zeros(M, Nn + 8, device=DEV)
-    out = big[:, 4:4 + Nn]  # strided, 16-B misaligned destination
+    out = big[:, 4:4 + Nn]  # strided destination; its rows are 16-B ALIGNED wherever Nn % 4 == 0 (offset 4 floats, ld = Nn + 8)
     ops.gemm(layout, Ad, Wd, out, M, Nn, K, bias=bias.to(DEV))
     scale = float(ref.abs().max())
     assert float((out.cpu().double() - ref).abs().max()) < 3e-6 * math.sqrt(K) * scale

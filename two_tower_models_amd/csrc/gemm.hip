@@ -367,6 +367,8 @@ static int launch_gemm_v(const GemmArgs& g, hipStream_t st) {
     if (e != hipSuccess) { set_error("gemm_kernel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
     lds_opt_in = true;
   }
+  // the launch counters name the tile and the FULL form: tests assert which one a shape lands on
+  ProfScope prof(BM == 128 ? (FULL ? "gemm_tile128_full" : "gemm_tile128") : (FULL ? "gemm_tile64_full" : "gemm_tile64"), st);
   gemm_kernel<BM, BN, A_KC, B_KC, FULL><<<grid, 256, lds, st>>>(g);
   return check_launch("gemm_kernel");
 }
@@ -461,6 +463,7 @@ static int gemm_impl(int layout, int64_t M, int64_t N, int64_t K, const float* A
     const int64_t blocks = ceil_div(total, 256) < 2048 ? ceil_div(total, 256) : 2048;
     // with a_colsum: ceil(M / 64) extra workgroups reduce the per-split column-sum partials, in split order
     const int64_t extra = a_colsum ? ceil_div(M, 64) : 0;
+    ProfScope prof("splitk_reduce_kernel", st);
     splitk_reduce_kernel<<<(unsigned)(blocks + extra), 256, 0, st>>>(reinterpret_cast<const float*>(ws), g, (int)blocks, cs_part, a_colsum);
     if ((rc = check_launch("splitk_reduce_kernel"))) return rc;
   }
