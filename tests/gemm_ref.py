@@ -721,15 +721,16 @@ def measure(cls, band):
 
 # ------------------------------------------------------------------ the GPU call (test_gpu_gemm_reference.py and its child)
 class Launches:
-    """with Launches() as n: ...  -> n[kernel] = launches the library counted inside the block, for every name of KERNELS."""
+    """with Launches() as n: ...  -> n[kernel] = launches the library counted inside the block, for every name of KERNELS
+    (or of `kernels`: tower_ref.py counts its own family)."""
 
-    def __init__(self):
-        self.n = {}
+    def __init__(self, kernels=KERNELS):
+        self.n, self.kernels = {}, tuple(kernels)
 
     def __enter__(self):
         from two_tower_models_amd import _native as N
         lib = N.load()
-        lib.tt_profile_filter(",".join(KERNELS).encode())
+        lib.tt_profile_filter(",".join(self.kernels).encode())
         lib.tt_profile_enable(1)
         return self.n
 
@@ -739,7 +740,7 @@ class Launches:
         lib = N.load()
         torch.cuda.synchronize()
         try:
-            for k in KERNELS:
+            for k in self.kernels:
                 ms, cnt = C.c_double(0.0), C.c_int64(0)
                 N.check(lib.tt_profile_read(k.encode(), C.byref(ms), C.byref(cnt)), "tt_profile_read")
                 self.n[k] = cnt.value

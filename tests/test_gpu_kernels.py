@@ -909,7 +909,10 @@ def test_gemm_weights_stationary_path(T, layout, M, Nn, K):
 def test_tower_weight_gradients_kernel_vs_fp64(T, B, D, F):
     """tt_tower_bwd_weights with one side (block partials in one launch + one reduce) on its own: dW3 = dy^T tin, dW2 = d_f^T h,
     dW1 = dh^T x and the three bias sums against float64 products, incl. a ragged last 64-row block, one row, F = 64;
-    and bit-identical from call to call (the reduce adds the partials in block order)."""
+    and bit-identical from call to call (the reduce adds the partials in block order).
+    (Through the autograd wrappers, packed operands, allclose tolerances: a smoke of the wrappers.  The kernels themselves
+    -- every instantiation, leading dimension, boundary and refusal at the C ABI against float64 with a derived bound --
+    are test_gpu_tower_reference.py's, tests/tower_ref.py.)"""
     ops, N = T
     g = torch.Generator().manual_seed(B * 7 + D)
     dy, tin, d_f = torch.randn(B, D, generator=g), torch.randn(B, 2 * D, generator=g), torch.randn(B, D, generator=g)
@@ -931,7 +934,10 @@ def test_fused_tower_with_third_input_block_forward_and_backward(T, B, D, F, n_r
     [ id | MLP | recent | mean ] -> Linear(4D -> D) (ref:src/two_tower_with_user_history_encoder.py:81-83,85-122) as one
     kernel per direction, against the same lines in float64 torch on the CPU: output, all six parameter gradients, the
     embedding-row gradients and the gradient that flows back into the encoder summary; ragged last block, one row,
-    duplicate ids; the extra block as a strided view; bit-identical from call to call."""
+    duplicate ids; the extra block as a strided view; bit-identical from call to call.
+    (Through the autograd wrappers, packed operands, allclose tolerances: a smoke of the wrappers.  The kernels themselves
+    -- every instantiation, leading dimension, boundary and refusal at the C ABI against float64 with a derived bound --
+    are test_gpu_tower_reference.py's, tests/tower_ref.py.)"""
     ops, N = T
     gen = torch.Generator().manual_seed(3 * B + D)
     p = {"emb": torch.randn(n_rows, D, generator=gen), "W1": torch.randn(256, F, generator=gen) * 0.3,
@@ -972,7 +978,10 @@ def test_fused_tower_with_third_input_block_forward_and_backward(T, B, D, F, n_r
 def test_fused_tower_matches_oracle_forward_and_backward(T, B, D, F, n_rows):
     """tt_tower_fwd / tt_tower_bwd_data with one side (one launch per direction: lookup + feature MLP + cat + tower Linear,
     ref:src/two_tower_base_retrieval.py:129-219) against the CPU oracle's item tower: output, every parameter gradient,
-    and the embedding-row gradients (dense form), incl. duplicate ids and a ragged last 64-row block."""
+    and the embedding-row gradients (dense form), incl. duplicate ids and a ragged last 64-row block.
+    (Through the autograd wrappers, packed operands, allclose tolerances: a smoke of the wrappers.  The kernels themselves
+    -- every instantiation, leading dimension, boundary and refusal at the C ABI against float64 with a derived bound --
+    are test_gpu_tower_reference.py's, tests/tower_ref.py.)"""
     ops, N = T
     gen = torch.Generator().manual_seed(B + D)
     p = {"item_id_embedding_arch.weight": torch.randn(n_rows, D, generator=gen),
@@ -1003,7 +1012,10 @@ def test_fused_tower_matches_oracle_forward_and_backward(T, B, D, F, n_rows):
 @pytest.mark.parametrize("B,D,Fu,Fi", [(300, 64, 5, 20), (8192, 128, 8, 8), (4096, 32, 16, 3), (33, 128, 8, 8)])
 def test_tower_pair_launches_are_the_single_tower_kernels_bit_for_bit(B, D, Fu, Fi):
     """tt_tower_* with two sides (both towers of the base model per launch: ops.FusedTowerPair) against two ops.FusedTower calls:
-    embeddings and every gradient -- table rows, the six weight / bias tensors of each tower -- identical bits."""
+    embeddings and every gradient -- table rows, the six weight / bias tensors of each tower -- identical bits.
+    (Through the autograd wrappers, packed operands, allclose tolerances: a smoke of the wrappers.  The kernels themselves
+    -- every instantiation, leading dimension, boundary and refusal at the C ABI against float64 with a derived bound --
+    are test_gpu_tower_reference.py's, tests/tower_ref.py.)"""
     import torch.nn as nn
     from two_tower_models_amd import ops
     dev = torch.device("cuda:0")

@@ -6,7 +6,7 @@
 //   backward  d_tin = dy W3;  d_emb = d_tin[:, :D] (the embedding-row gradients);  d_f = d_tin[:, D:];
 //             dh = (d_f W2) (.) [h > 0]          (autograd of the same lines, data side)
 // The weight gradients (dW3 = dy^T tin, dW2 = d_f^T h, dW1 = dh^T x and the three bias sums) are reductions over
-// the batch and stay with tt_gemm_tn_colsum_f32.
+// the batch: tower_wgrad_kernel below (one partial per 64-row block) and its deterministic reduce.
 //
 // One workgroup = 64 batch rows, 4 waves.  The row block's activations live in LDS ([64][K + 4] images, the layout
 // of mfma_stream.hpp's register-staged tiles), each wave owns 32 output columns and holds their weights in
@@ -570,6 +570,7 @@ static int tower_launch(void (*kernel)(Args), const char* name, dim3 grid, size_
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e)); return (int)e; }
   }
+  ProfScope prof(name, st);
   kernel<<<grid, 256, lds, st>>>(a);
   return check_launch(name);
 }
@@ -578,15 +579,15 @@ static int tower_launch(void (*kernel)(Args), const char* name, dim3 grid, size_
 // function per kernel family, in this order: it is the order the kernels are instantiated in, and so the order of the
 // device code.
 static int tower_fwd_one(const TowerFwdArgs& a, int64_t D, int64_t E, int rt, dim3 grid, size_t lds, hipStream_t st) {
-#define TT_L(E8, X) (rt == 1 ? tower_launch(tower_fwd_kernel<E8, X, 1>, "tower_fwd_kernel", grid, lds, st, a) \
-                             : tower_launch(tower_fwd_kernel<E8, X, 2>, "tower_fwd_kernel", grid, lds, st, a))
+#define TT_L(E8, X) (rt == 1 ? tower_launch(tower_fwd_kernel<E8, X, 1>, "tower_fwd_kernel_r1", grid, lds, st, a) \
+                             : tower_launch(tower_fwd_kernel<E8, X, 2>, "tower_fwd_kernel_r2", grid, lds, st, a))
   if (E == 0) return D == 32 ? TT_L(4, false) : D == 64 ? TT_L(8, false) : TT_L(16, false);
   return D == 32 ? TT_L(4, true) : D == 64 ? TT_L(8, true) : TT_L(16, true);
 #undef TT_L
 }
 static int tower_bwd_one(const TowerBwdArgs& a, int64_t D, int64_t E, int rt, dim3 grid, hipStream_t st) {
-#define TT_L(E8, X) (rt == 1 ? tower_launch(tower_bwd_kernel<E8, X, 1>, "tower_bwd_kernel", grid, 0, st, a) \
-                             : tower_launch(tower_bwd_kernel<E8, X, 2>, "tower_bwd_kernel", grid, 0, st, a))
+#define TT_L(E8, X) (rt == 1 ? tower_launch(tower_bwd_kernel<E8, X, 1>, "tower_bwd_kernel_r1", grid, 0, st, a) \
+                             : tower_launch(tower_bwd_kernel<E8, X, 2>, "tower_bwd_kernel_r2", grid, 0, st, a))
   if (E == 0) return D == 32 ? TT_L(4, false) : D == 64 ? TT_L(8, false) : TT_L(16, false);
   return D == 32 ? TT_L(4, true) : D == 64 ? TT_L(8, true) : TT_L(16, true);
 #undef TT_L
@@ -598,14 +599,14 @@ static int tower_wgrad_one(const TowerWgradArgs& a, int64_t D, int64_t E, dim3 g
 #undef TT_L
 }
 static int tower_fwd_two(const TowerFwdArgs2& q, int64_t D, int rt, dim3 grid, size_t lds, hipStream_t st) {
-#define TT_L(E8) (rt == 1 ? tower_launch(tower_fwd_pair_kernel<E8, 1>, "tower_fwd_pair_kernel", grid, lds, st, q) \
-                          : tower_launch(tower_fwd_pair_kernel<E8, 2>, "tower_fwd_pair_kernel", grid, lds, st, q))
+#define TT_L(E8) (rt == 1 ? tower_launch(tower_fwd_pair_kernel<E8, 1>, "tower_fwd_pair_kernel_r1", grid, lds, st, q) \
+                          : tower_launch(tower_fwd_pair_kernel<E8, 2>, "tower_fwd_pair_kernel_r2", grid, lds, st, q))
   return D == 32 ? TT_L(4) : D == 64 ? TT_L(8) : TT_L(16);
 #undef TT_L
 }
 static int tower_bwd_two(const TowerBwdArgs2& q, int64_t D, int rt, dim3 grid, hipStream_t st) {
-#define TT_L(E8) (rt == 1 ? tower_launch(tower_bwd_pair_kernel<E8, 1>, "tower_bwd_pair_kernel", grid, 0, st, q) \
-                          : tower_launch(tower_bwd_pair_kernel<E8, 2>, "tower_bwd_pair_kernel", grid, 0, st, q))
+#define TT_L(E8) (rt == 1 ? tower_launch(tower_bwd_pair_kernel<E8, 1>, "tower_bwd_pair_kernel_r1", grid, 0, st, q) \
+                          : tower_launch(tower_bwd_pair_kernel<E8, 2>, "tower_bwd_pair_kernel_r2", grid, 0, st, q))
   return D == 32 ? TT_L(4) : D == 64 ? TT_L(8) : TT_L(16);
 #undef TT_L
 }
@@ -675,11 +676,13 @@ extern "C" int tt_tower_bwd_weights(const tt_tower_wgrad_side* sides, int32_t n_
   const unsigned reduce_blocks = (unsigned)ceil_div(part_max, 64);
   if (n_sides == 1) {
     if (int rc = tower_wgrad_one(q.t[0], D, E, grid, lds, st)) return rc;
+    ProfScope prof("tower_wgrad_reduce_kernel", st);
     tower_wgrad_reduce_kernel<<<reduce_blocks, 1024, 0, st>>>(r.part[0], (int)blocks, r.part_floats[0], r.n3[0], r.n2[0], r.n1[0], D,
                                                               r.dW3[0], r.dW2[0], r.dW1[0], r.db3[0], r.db2[0], r.db1[0]);
     return check_launch("tower_wgrad_reduce_kernel");
   }
   if (int rc = tower_wgrad_two(q, D, grid, lds, st)) return rc;
+  ProfScope prof("tower_wgrad_reduce_pair_kernel", st);
   tower_wgrad_reduce_pair_kernel<<<dim3(reduce_blocks, 2), 1024, 0, st>>>(r, (int)blocks, D);
   return check_launch("tower_wgrad_reduce_pair_kernel");
 }
