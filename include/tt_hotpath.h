@@ -569,7 +569,11 @@ int tt_attn_bwd(const float* qkv, const float* ctx, const float* lse, const floa
  * the composed parameters w_in = W_in W_o, b_in = W_in b_o + b_in (q, k, v are linear in the never-formed output) and maps
  * dW_in / db_in back itself (ops.HistoryEncoder).
  * Shapes: H <= 64, D <= 128, D % 4 == 0, D % heads == 0, (D / heads) % 4 == 0, heads <= 16 (tt_enc_last_supported);
- * x, dx, d_recent, the weights, t, xbar and ws 16-byte aligned. */
+ * x, dx, d_recent, the weights, t, xbar and ws 16-byte aligned.
+ * Refusals, before anything is launched or written: a shape outside the above or a leading dimension below D is
+ * TT_E_UNSUPPORTED; a null pointer, B < 0, a misaligned operand or ld_dr % 4 != 0 is TT_E_BADARG; ws_bytes below
+ * tt_enc_last_bwd_workspace_bytes is TT_E_WORKSPACE.  B = 0 is accepted: nothing is written, except that the weight half
+ * writes zero gradients. */
 int tt_enc_last_supported(int64_t H, int64_t D, int64_t heads);
 int tt_enc_last_fwd(const float* x, int64_t B, int64_t H, int64_t D, int64_t heads, const float* w_in,
                     const float* b_in, const float* w_out, const float* b_out, float* recent, int64_t ld_recent,

@@ -588,7 +588,8 @@ static int enc_last_fwd_any(const float* x, int64_t B, int64_t H, int64_t D, int
                             int64_t ld_recent, float* q0, float* t, float* probs, float* xbar, float* ctx0, tt_stream_t stream) {
   if (!x || !w_in || !b_in || !w_out || !b_out || !recent || !q0 || !t || !probs || !xbar || !ctx0)
     return fail_arg("tt_enc_last_fwd: null pointer");
-  if (B < 0 || !tt_enc_last_supported(H, D, heads) || ld_recent < D) {
+  if (B < 0) return fail_arg("tt_enc_last_fwd: negative batch");
+  if (!tt_enc_last_supported(H, D, heads) || ld_recent < D) {
     set_error("tt_enc_last_fwd: shape outside H <= 64, D <= 128, D %% 4 == 0, head width %% 4 == 0 (H = %lld, D = %lld, heads = %lld)",
               (long long)H, (long long)D, (long long)heads);
     return TT_E_UNSUPPORTED;
@@ -604,20 +605,25 @@ static int enc_last_fwd_any(const float* x, int64_t B, int64_t H, int64_t D, int
   a.q0 = q0; a.t = t; a.xbar = xbar; a.ctx0 = ctx0;
   a.recent = recent; a.ld_recent = ld_recent;
   int rc;
-  enc_last_pre_kernel<<<G, 256, el_small_lds(D), st>>>(a);
-  if ((rc = check_launch("enc_last_pre_kernel"))) return rc;
+  {
+    ProfScope prof("enc_last_pre_kernel", st);
+    enc_last_pre_kernel<<<G, 256, el_small_lds(D), st>>>(a);
+    if ((rc = check_launch("enc_last_pre_kernel"))) return rc;
+  }
   {
     const size_t lds = ((size_t)H * (D + 4) + heads * D) * sizeof(float);
     if ((rc = lengths ? el_opt_in(enc_last_main_fwd_kernel<true>, lds, "enc_last_main_fwd_kernel")
                       : el_opt_in(enc_last_main_fwd_kernel<false>, lds, "enc_last_main_fwd_kernel")))
       return rc;
-    ProfScope prof("enc_last_main_fwd_kernel", st);
+    // the launch counters tell the two instantiations apart
+    ProfScope prof(lengths ? "enc_last_main_fwd_len_kernel" : "enc_last_main_fwd_kernel", st);
     if (lengths)
       enc_last_main_fwd_kernel<true><<<(unsigned)B, 256, lds, st>>>(x, (int)H, (int)D, (int)heads, lengths, t, probs, xbar);
     else
       enc_last_main_fwd_kernel<false><<<(unsigned)B, 256, lds, st>>>(x, (int)H, (int)D, (int)heads, nullptr, t, probs, xbar);
     if ((rc = check_launch("enc_last_main_fwd_kernel"))) return rc;
   }
+  ProfScope prof("enc_last_post_kernel", st);
   enc_last_post_kernel<<<G, 256, el_small_lds(D), st>>>(a);
   return check_launch("enc_last_post_kernel");
 }
@@ -661,15 +667,17 @@ extern "C" int tt_enc_last_bwd_data(const float* x, int64_t B, int64_t H, int64_
                                     const float* w_out, const float* d_recent, int64_t ld_dr, const float* t,
                                     const float* probs, float* dx, void* ws, int64_t ws_bytes, tt_stream_t stream) {
   if (!x || !w_in || !w_out || !d_recent || !t || !probs || !dx) return fail_arg("tt_enc_last_bwd_data: null pointer");
-  if (B < 0 || !tt_enc_last_supported(H, D, heads) || ld_dr < D) {
+  if (B < 0) return fail_arg("tt_enc_last_bwd: negative batch");
+  if (!tt_enc_last_supported(H, D, heads) || ld_dr < D) {
     set_error("tt_enc_last_bwd: shape outside H <= 64, D <= 128, D %% 4 == 0, head width %% 4 == 0");
     return TT_E_UNSUPPORTED;
   }
   if (!el_aligned(x) || !el_aligned(w_in) || !el_aligned(w_out) || !el_aligned(t) || !el_aligned(dx) || !el_aligned(ws) ||
       !el_aligned(d_recent) || (ld_dr % 4) != 0)
-    return fail_arg("tt_enc_last_bwd: x, dx, w_in, w_out, t, xbar, d_recent, ws must be 16-byte aligned, ld_dr % 4 == 0");
+    return fail_arg("tt_enc_last_bwd: x, dx, w_in, w_out, t, d_recent, ws must be 16-byte aligned, ld_dr % 4 == 0");
   if (B == 0) return 0;
-  if (!ws || ws_bytes < tt_enc_last_bwd_workspace_bytes(B, H, D, heads)) return fail_arg("tt_enc_last_bwd: workspace too small");
+  if (!ws) return fail_arg("tt_enc_last_bwd: null workspace");
+  if (ws_bytes < tt_enc_last_bwd_workspace_bytes(B, H, D, heads)) { set_error("tt_enc_last_bwd: workspace too small"); return TT_E_WORKSPACE; }
   hipStream_t st = S(stream);
   const int64_t G = el_groups(B);
   ElArgs a{};
@@ -680,8 +688,11 @@ extern "C" int tt_enc_last_bwd_data(const float* x, int64_t B, int64_t H, int64_
   el_carve(a, ws, B, D, heads);
   a.dx = dx;
   int rc;
-  enc_last_bwd_a_kernel<<<(unsigned)G, 256, el_small_lds(D), st>>>(a);
-  if ((rc = check_launch("enc_last_bwd_a_kernel"))) return rc;
+  {
+    ProfScope prof("enc_last_bwd_a_kernel", st);
+    enc_last_bwd_a_kernel<<<(unsigned)G, 256, el_small_lds(D), st>>>(a);
+    if ((rc = check_launch("enc_last_bwd_a_kernel"))) return rc;
+  }
   {
     const size_t lds = ((size_t)H * (D + 4) + 2 * heads * D + 2 * heads * 64) * sizeof(float);
     if ((rc = el_opt_in(enc_last_main_bwd_kernel, lds, "enc_last_main_bwd_kernel"))) return rc;
@@ -689,6 +700,7 @@ extern "C" int tt_enc_last_bwd_data(const float* x, int64_t B, int64_t H, int64_
     enc_last_main_bwd_kernel<<<(unsigned)B, 256, lds, st>>>(x, (int)H, (int)D, (int)heads, t, probs, a.d_xbar, a.dt, dx);
     if ((rc = check_launch("enc_last_main_bwd_kernel"))) return rc;
   }
+  ProfScope prof("enc_last_bwd_b_kernel", st);
   enc_last_bwd_b_kernel<<<(unsigned)G, 256, el_small_lds(D), st>>>(a);
   return check_launch("enc_last_bwd_b_kernel");
 }
@@ -699,7 +711,8 @@ extern "C" int tt_enc_last_bwd_weights(const float* x, int64_t B, int64_t H, int
                                        tt_stream_t stream) {
   if (!x || !d_recent || !q0 || !xbar || !ctx0 || !dW_in || !db_in || !dW_out || !db_out)
     return fail_arg("tt_enc_last_bwd_weights: null pointer");
-  if (B < 0 || !tt_enc_last_supported(H, D, heads) || ld_dr < D) {
+  if (B < 0) return fail_arg("tt_enc_last_bwd: negative batch");
+  if (!tt_enc_last_supported(H, D, heads) || ld_dr < D) {
     set_error("tt_enc_last_bwd: shape outside H <= 64, D <= 128, D %% 4 == 0, head width %% 4 == 0");
     return TT_E_UNSUPPORTED;
   }
@@ -713,7 +726,8 @@ extern "C" int tt_enc_last_bwd_weights(const float* x, int64_t B, int64_t H, int
     (void)hipMemsetAsync(db_out, 0, sizeof(float) * D, st);
     return 0;
   }
-  if (!ws || ws_bytes < tt_enc_last_bwd_workspace_bytes(B, H, D, heads)) return fail_arg("tt_enc_last_bwd: workspace too small");
+  if (!ws) return fail_arg("tt_enc_last_bwd: null workspace");
+  if (ws_bytes < tt_enc_last_bwd_workspace_bytes(B, H, D, heads)) { set_error("tt_enc_last_bwd: workspace too small"); return TT_E_WORKSPACE; }
   const int64_t G = el_groups(B);
   ElArgs a{};
   a.x = x;
@@ -722,9 +736,13 @@ extern "C" int tt_enc_last_bwd_weights(const float* x, int64_t B, int64_t H, int
   a.d_recent = d_recent; a.ld_dr = ld_dr;
   el_carve(a, ws, B, D, heads);
   int rc;
-  enc_last_wgrad_kernel<<<dim3((unsigned)G, 2), 256, 0, st>>>(a);
-  if ((rc = check_launch("enc_last_wgrad_kernel"))) return rc;
+  {
+    ProfScope prof("enc_last_wgrad_kernel", st);
+    enc_last_wgrad_kernel<<<dim3((unsigned)G, 2), 256, 0, st>>>(a);
+    if ((rc = check_launch("enc_last_wgrad_kernel"))) return rc;
+  }
   const int total = (int)(4 * D * D + 3 * D);
+  ProfScope prof("enc_last_reduce_kernel", st);
   enc_last_reduce_kernel<<<(unsigned)ceil_div(total, 256), 256, 0, st>>>(a.part_a, a.part_b, (int)G, (int)D, dW_in, db_in, dW_out, db_out);
   return check_launch("enc_last_reduce_kernel");
 }
@@ -734,6 +752,8 @@ extern "C" int tt_enc_last_bwd(const float* x, int64_t B, int64_t H, int64_t D, 
                                const float* probs, const float* xbar, const float* ctx0, float* dx, float* dW_in, float* db_in,
                                float* dW_out, float* db_out, void* ws, int64_t ws_bytes, tt_stream_t stream) {
   if (!q0 || !xbar || !ctx0 || !dW_in || !db_in || !dW_out || !db_out) return fail_arg("tt_enc_last_bwd: null pointer");
+  // what only the weight half checks, before the data half launches anything
+  if (!el_aligned(xbar)) return fail_arg("tt_enc_last_bwd: xbar must be 16-byte aligned");
   const int rc = tt_enc_last_bwd_data(x, B, H, D, heads, w_in, w_out, d_recent, ld_dr, t, probs, dx, ws, ws_bytes, stream);
   if (rc) return rc;
   return tt_enc_last_bwd_weights(x, B, H, D, heads, d_recent, ld_dr, q0, xbar, ctx0, dW_in, db_in, dW_out, db_out, ws, ws_bytes,

@@ -182,8 +182,11 @@ extern "C" int tt_gather_rows(const float* table, int64_t n_rows, int64_t dim, c
   if (n_rows <= 0 || dim <= 0 || n_ids < 0 || ld_out < dim) return fail_arg("tt_gather_rows: sizes");
   if (n_ids == 0) return 0;
   const bool vec = (dim % 4 == 0) && (ld_out % 4 == 0) && aligned16(table) && aligned16(out);
+  const int64_t dv = dim / 4;
+  ProfScope prof(!vec ? "gather_rows_kernel_v1_l64" : dv <= 8 ? "gather_rows_kernel_v4_l8" : dv <= 16 ? "gather_rows_kernel_v4_l16"
+                                                                                                       : "gather_rows_kernel_v4_l32",
+                 S(stream));
   if (vec) {
-    const int64_t dv = dim / 4;
     if (dv <= 8)
       gather_rows_kernel<4, 8><<<ceil_div(n_ids, 32), 256, 0, S(stream)>>>(table, n_rows, dv, ids, n_ids, out, ld_out / 4, oob_flag);
     else if (dv <= 16)
@@ -224,10 +227,13 @@ static int hist_embed_pool_any(const float* table, int64_t n_rows, int64_t dim, 
   if (B == 0) return 0;
   const bool vec = (dim % 4 == 0) && (ld_pooled % 4 == 0) && aligned16(table) && aligned16(x) &&
                    aligned16(pooled) && (!pe || aligned16(pe));
+  const char* name = vec ? (lengths ? "hist_embed_pool_len_kernel_v4" : "hist_embed_pool_kernel_v4")
+                         : (lengths ? "hist_embed_pool_len_kernel_v1" : "hist_embed_pool_kernel_v1");
   if (vec) {
     const int64_t dv = dim / 4;
     const size_t lds = (size_t)(256 / 32) * dv * sizeof(float4);
     if (lds > 64 * 1024) { set_error("tt_hist_embed_pool: dim too large"); return TT_E_UNSUPPORTED; }
+    ProfScope prof(name, S(stream));
     if (lengths)
       hist_embed_pool_kernel<4, 32, true><<<B, 256, lds, S(stream)>>>(table, n_rows, dv, ids, H, lengths, pe, x, pooled, ld_pooled / 4, oob_flag);
     else
@@ -235,6 +241,7 @@ static int hist_embed_pool_any(const float* table, int64_t n_rows, int64_t dim, 
   } else {
     const size_t lds = (size_t)(256 / 64) * dim * sizeof(float);
     if (lds > 64 * 1024) { set_error("tt_hist_embed_pool: dim too large"); return TT_E_UNSUPPORTED; }
+    ProfScope prof(name, S(stream));
     if (lengths)
       hist_embed_pool_kernel<1, 64, true><<<B, 256, lds, S(stream)>>>(table, n_rows, dim, ids, H, lengths, pe, x, pooled, ld_pooled, oob_flag);
     else
@@ -279,6 +286,7 @@ extern "C" int tt_hist_pool_bwd(float* dx, int64_t B, int64_t H, int64_t dim, co
   if (B == 0) return 0;
   const int64_t total = B * H * dim;
   const int64_t blocks = ceil_div(total, 256) < 4096 ? ceil_div(total, 256) : 4096;
+  ProfScope prof("hist_pool_bwd_kernel", S(stream));
   hist_pool_bwd_kernel<<<(unsigned)blocks, 256, 0, S(stream)>>>(dx, B, H, dim, d_pooled, ld_pooled);
   return check_launch("hist_pool_bwd_kernel");
 }
@@ -291,6 +299,7 @@ extern "C" int tt_hist_pool_bwd_len(float* dx, int64_t B, int64_t H, int64_t dim
   if (B == 0) return 0;
   const int64_t total = B * H * dim;
   const int64_t blocks = ceil_div(total, 256) < 4096 ? ceil_div(total, 256) : 4096;
+  ProfScope prof("hist_pool_bwd_len_kernel", S(stream));
   hist_pool_bwd_len_kernel<<<(unsigned)blocks, 256, 0, S(stream)>>>(dx, B, H, dim, lengths, d_pooled, ld_pooled);
   return check_launch("hist_pool_bwd_len_kernel");
 }
