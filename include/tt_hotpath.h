@@ -466,6 +466,31 @@ int tt_adam_tables_finish(const tt_adam_finish_job* jobs, int32_t n_jobs, const 
  * the step's critical path.  planes = 7 is tt_adam_begin_ids.  At most 4 tables. */
 int tt_adam_begin_ids_planes(double* hyper, float* tab, int64_t tab_steps, const tt_adam_stash_job* jobs, int32_t n_jobs,
                              int32_t planes, tt_stream_t stream);
+/* The chained schedule: a step that looks up FEW rows marks them too, so that nothing is parked in front of the sweep or
+ * written back behind it and the next step's sweep follows this one's on the sweep's stream with one launch in between:
+ *   tt_adam_mark_advance          sets the bit of every id of every job (bitmaps as for tt_adam_mark_rows, but CLEARED BY THE
+ *                                 CALLER beforehand, off the critical path) and advances the step count like tt_adam_advance
+ *                                 -- ONE launch; 0..4 jobs
+ *   tt_adam_tables_sweep_chained  tt_adam_tables_sweep_marked with every p / m / v triple of a lane in flight (the depth of
+ *                                 tt_adam_tables_sweep: it runs as that kernel, adam_sweep_tables_kernel) -- and it can thin
+ *                                 itself while it runs: once the device word *alone_flag holds `tag`, the workgroups numbered
+ *                                 alone_wgs and up finish the chunk they hold and leave, the others take the rest.  The caller
+ *                                 writes the step number there when nothing else is left to run beside the sweep (alone on
+ *                                 the chip, fewer resident waves stream better); a tag of another step never matches, nothing
+ *                                 has to be cleared.  alone_flag == NULL, alone_wgs <= 0 or alone_wgs >= the launch's
+ *                                 workgroups: never thins.
+ * Same bits as tt_adam_tables_sweep_marked whatever the flag does.  (ref:train/train.py:123-125: the dense Adam step.) */
+typedef struct {
+  const int64_t* ids;
+  int64_t n_ids, n_rows;
+  uint32_t* marks;
+  int64_t marks_words;
+} tt_adam_mark_job;
+int tt_adam_mark_advance(double* hyper, const tt_adam_mark_job* jobs /*host*/, int32_t n_jobs, tt_stream_t stream);
+int tt_adam_tables_sweep_chained(const struct tt_adam_tensor_s* tables /*host*/, const int64_t* dims /*host*/,
+                                 const uint32_t* const* marks /*host array of device pointers*/, int32_t n_tables,
+                                 const double* hyper, int32_t n_wgs, int32_t alone_wgs, const uint32_t* alone_flag,
+                                 uint32_t tag, tt_stream_t stream);
 
 /* A HIP stream of the device's least priority (hipStreamCreateWithPriority) for
  * tt_adam_table_sweep, so the backward pass on the caller's stream is dispatched first. */

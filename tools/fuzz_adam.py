@@ -1,7 +1,7 @@
 """Randomised multi-step check of the optimiser schedules: random model kind / shapes, 2-5 train steps whose batches
 share some ids and not others (rows that are looked up, rest for a step or two on momentum alone, and are looked up
-again), random DenseExactAdam schedule (serial sweep, sweep started by zero_grad, sweep started by the forward,
-deferred = lazy + flush).  Against the oracle's torch.optim.Adam-semantics trajectory: every loss (1e-4), never
+again), every DenseExactAdam schedule (serial sweep, sweep started by zero_grad, sweep started by the forward with
+rows parked / marked / chained, deferred = lazy + flush).  Against the oracle's torch.optim.Adam-semantics trajectory: every loss (1e-4), never
 looked-up rows bit-identical, every other table row and every dense parameter within 5e-6 for all but 0.5 % of a
 tensor's elements and within steps * 2.2 lr for all (Adam's early steps are sign-sensitive on near-zero gradients,
 tests/test_gpu_models.py).  The schedules must also agree with EACH OTHER bit for bit.
@@ -23,8 +23,11 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 # "marked": the forward schedule with the big-lookup threshold lowered to 1 -- rows marked for the sweep to step over where the
 # row width allows (32 / 64 / 128), moments parked on the sweep's stream otherwise
+# "chained": the forward schedule as it is by default -- where the row width allows, rows marked, the finish ahead of the sweep,
+# the next sweep right behind this one (TT_ADAM_CHAIN=0 in the two schedules above it: rows parked / marked, steps in series);
+# its steps run with no host synchronisation between them
 SCHEDULES = [dict(overlap_sweep=False), dict(overlap_sweep=True), dict(overlap_sweep="forward"), dict(lazy=True),
-             dict(overlap_sweep="forward", marked=True)]
+             dict(overlap_sweep="forward", marked=True), dict(overlap_sweep="forward", chained=True)]
 t0, n, bad = time.time(), 0, 0
 while time.time() - t0 < budget:
     kind = str(rng.choice(["base", "base", "hist"]))
@@ -67,14 +70,16 @@ while time.time() - t0 < budget:
             model.load_state_dict(init)
             model = model.to(DEV)
             A.optim._SPLIT_MIN_IDS = 1 if sched.get("marked") else 65536
-            opt = A.DenseExactAdam(model.parameters(), lr=1e-3, **{k: v for k, v in sched.items() if k != "marked"})
+            os.environ["TT_ADAM_CHAIN"] = "1" if sched.get("chained") else "0"
+            opt = A.DenseExactAdam(model.parameters(), lr=1e-3, **{k: v for k, v in sched.items() if k not in ("marked", "chained")})
             losses = []
             for b in batches:
                 loss = model.train_forward(*[t.to(DEV) for t in b])
                 opt.zero_grad()
                 loss.backward()
                 opt.step()
-                losses.append(loss.item())
+                losses.append(loss.detach() if sched.get("chained") else loss.item())
+            losses = [float(x) for x in losses]
             if sched.get("lazy"):
                 opt.flush()
             torch.cuda.synchronize()

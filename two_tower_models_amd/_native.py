@@ -45,6 +45,12 @@ class AdamTensor(C.Structure):
     _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", _i64)]
 
 
+class AdamMarkJob(C.Structure):
+    """tt_adam_mark_job."""
+
+    _fields_ = [("ids", _vp), ("n_ids", _i64), ("n_rows", _i64), ("marks", _vp), ("marks_words", _i64)]
+
+
 class AdamStashJob(C.Structure):
     """tt_adam_stash_job."""
 
@@ -176,6 +182,9 @@ SIGNATURES = {
     "tt_adam_marked_supported": (_int, [_i64]),
     "tt_adam_mark_rows": (_int, [_vp, _i64, _i64, _vp, _i64, _vp]),
     "tt_adam_tables_sweep_marked": (_int, [C.POINTER(AdamTensor), C.POINTER(_i64), C.POINTER(_vp), _i32, _vp, _i32, _vp]),
+    "tt_adam_mark_advance": (_int, [_vp, C.POINTER(AdamMarkJob), _i32, _vp]),
+    "tt_adam_tables_sweep_chained": (_int, [C.POINTER(AdamTensor), C.POINTER(_i64), C.POINTER(_vp), _i32, _vp, _i32, _i32, _vp,
+                                            C.c_uint32, _vp]),
     "tt_adam_table_finish": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, C.POINTER(GradSources), _i64, _vp, _vp, _vp,
                                     _vp, _vp, _i64, _vp]),
     "tt_adam_advance_tab": (_int, [_vp, _vp, _i64, _vp]),

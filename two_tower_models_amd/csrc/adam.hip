@@ -16,6 +16,8 @@
 //   p += -(lr/(1-b1^t)) * ( m / (sqrt(v)/sqrt(1-b2^t) + eps) )
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace tt {
@@ -94,7 +96,7 @@ __device__ __forceinline__ void step_consts_from_doubles(double lr, double b1, d
 }
 // tab (optional): per-step constants for the deferred schedule, tab[2j] = (float)(-h5_j),
 // tab[2j+1] = (float)(1 / h6_j) -- the values every dense kernel of step j saw
-__global__ void adam_advance_kernel(double* h, float* tab, int64_t tab_cap) {
+__device__ __forceinline__ void advance_step(double* h, float* tab, int64_t tab_cap) {
   const double step = h[4] + 1.0;
   h[4] = step;
   step_consts_from_doubles(h[0], h[1], h[2], step, h[5], h[6]);
@@ -104,6 +106,7 @@ __global__ void adam_advance_kernel(double* h, float* tab, int64_t tab_cap) {
     tab[2 * j + 1] = (float)(1.0 / h[6]);
   }
 }
+__global__ void adam_advance_kernel(double* h, float* tab, int64_t tab_cap) { advance_step(h, tab, tab_cap); }
 
 __device__ __forceinline__ const float* source_row(const tt_grad_sources& s, int64_t pos) {
   int k = 0;
@@ -252,16 +255,7 @@ __global__ __launch_bounds__(256) void adam_begin_ids_kernel(const StashJobs job
                                                              int advance) {
   const unsigned n_stash = jobs.first_block[jobs.n];
   if (blockIdx.x == n_stash) {
-    if (threadIdx.x == 0 && advance) {
-      const double step = h[4] + 1.0;
-      h[4] = step;
-      step_consts_from_doubles(h[0], h[1], h[2], step, h[5], h[6]);
-      const int64_t j = (int64_t)step;
-      if (tab && j < tab_cap) {
-        tab[2 * j] = (float)(-h[5]);
-        tab[2 * j + 1] = (float)(1.0 / h[6]);
-      }
-    }
+    if (threadIdx.x == 0 && advance) advance_step(h, tab, tab_cap);
     return;
   }
   int t = 0;
@@ -456,37 +450,76 @@ struct SweepTables {
   unsigned first_chunk[SWEEP_MAX_TABLES + 1];  // table t owns chunks [first_chunk[t], first_chunk[t + 1])
   int n;
 };
-template <int ITERS, int UNR>
-__global__ __launch_bounds__(256) void adam_sweep_tables_kernel(const SweepTables tabs, const double* __restrict__ hyper,
-                                                                unsigned* __restrict__ ctr) {
+// MARKS (the chained schedule's sweep, tt_adam_tables_sweep_chained): the step's looked-up rows are marked in a bitmap and
+// stepped over, exactly as in adam_sweep_tables_marked_kernel below (UNR = row triples of a lane in flight).  And it can THIN
+// itself: the thread that fetches the next chunk index also reads a device word (relaxed, agent scope); once the word holds
+// this launch's tag, a workgroup numbered alone_wgs or higher fetches no further index, finishes the chunk it holds and
+// leaves through the re-arm below -- the counter still hands out every index exactly once, to the workgroups that stay.
+// The host writes the tag (the step number: another step's write can never thin this launch, nothing has to be cleared)
+// when the main stream has run dry and the sweep has the chip to itself, where fewer resident waves stream better.
+struct SweepTablesMarked {
+  SweepTables t;
+  const unsigned* marks[SWEEP_MAX_TABLES];
+  int sh[SWEEP_MAX_TABLES];
+};
+struct SweepTablesChained {
+  SweepTablesMarked m;
+  const unsigned* alone_flag;  // nullptr: never thins
+  unsigned tag, alone_wgs;
+};
+constexpr unsigned SWEEP_NO_CHUNK = 0xffffffffu;  // (the entry points refuse 2^32 - 1 chunks or more)
+__device__ __forceinline__ unsigned next_chunk_or_leave(const SweepTablesChained& a, unsigned* ctr) {
+  if (a.alone_flag && blockIdx.x >= a.alone_wgs &&
+      __hip_atomic_load(a.alone_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.tag)
+    return SWEEP_NO_CHUNK;
+  return atomicAdd(&ctr[0], 1u);
+}
+template <int ITERS, int PAIR>
+__device__ __forceinline__ void sweep_chunk_marked(const SweepTablesMarked& tm, unsigned chu, const AdamConst& c);
+
+template <int ITERS, int UNR, bool MARKS = false>
+__global__ __launch_bounds__(256) void adam_sweep_tables_kernel(const std::conditional_t<MARKS, SweepTablesChained, SweepTables> tabs,
+                                                                const double* __restrict__ hyper, unsigned* __restrict__ ctr) {
   const AdamConst c = load_hyper(hyper);
-  const unsigned n_chunks = tabs.first_chunk[tabs.n];
+  unsigned n_chunks;
+  if constexpr (MARKS) n_chunks = tabs.m.t.first_chunk[tabs.m.t.n];
+  else n_chunks = tabs.first_chunk[tabs.n];
   __shared__ unsigned s_next[2];
-  if (threadIdx.x == 0) s_next[0] = atomicAdd(&ctr[0], 1u);
+  if (threadIdx.x == 0) {
+    if constexpr (MARKS) s_next[0] = next_chunk_or_leave(tabs, ctr);
+    else s_next[0] = atomicAdd(&ctr[0], 1u);
+  }
   __syncthreads();
   unsigned ch = s_next[0];
   int par = 0;
   while (ch < n_chunks) {
-    if (threadIdx.x == 0) s_next[par ^ 1] = atomicAdd(&ctr[0], 1u);
-    int t = 0;
+    if (threadIdx.x == 0) {
+      if constexpr (MARKS) s_next[par ^ 1] = next_chunk_or_leave(tabs, ctr);
+      else s_next[par ^ 1] = atomicAdd(&ctr[0], 1u);
+    }
+    if constexpr (MARKS) {
+      sweep_chunk_marked<ITERS, UNR>(tabs.m, __builtin_amdgcn_readfirstlane(ch), c);
+    } else {
+      int t = 0;
 #pragma unroll
-    for (int q = 1; q < SWEEP_MAX_TABLES; ++q)
-      if (q < tabs.n && ch >= tabs.first_chunk[q]) t = q;
-    float4* __restrict__ W = tabs.W[t];
-    float4* __restrict__ M = tabs.M[t];
-    float4* __restrict__ V = tabs.V[t];
-    const int64_t n4 = tabs.n4[t];
-    const int64_t base = (int64_t)(ch - tabs.first_chunk[t]) * (256 * ITERS) + threadIdx.x;
+      for (int q = 1; q < SWEEP_MAX_TABLES; ++q)
+        if (q < tabs.n && ch >= tabs.first_chunk[q]) t = q;
+      float4* __restrict__ W = tabs.W[t];
+      float4* __restrict__ M = tabs.M[t];
+      float4* __restrict__ V = tabs.V[t];
+      const int64_t n4 = tabs.n4[t];
+      const int64_t base = (int64_t)(ch - tabs.first_chunk[t]) * (256 * ITERS) + threadIdx.x;
 #pragma unroll UNR
-    for (int k = 0; k < ITERS; ++k) {
-      const int64_t i = base + (int64_t)k * 256;
-      if (i >= n4) break;
-      float4 p = sweep_load(W + i), m = sweep_load(M + i), v = sweep_load(V + i);
-      adam_elem_zero_grad(p.x, m.x, v.x, c);
-      adam_elem_zero_grad(p.y, m.y, v.y, c);
-      adam_elem_zero_grad(p.z, m.z, v.z, c);
-      adam_elem_zero_grad(p.w, m.w, v.w, c);
-      sweep_store(p, W + i); sweep_store(m, M + i); sweep_store(v, V + i);
+      for (int k = 0; k < ITERS; ++k) {
+        const int64_t i = base + (int64_t)k * 256;
+        if (i >= n4) break;
+        float4 p = sweep_load(W + i), m = sweep_load(M + i), v = sweep_load(V + i);
+        adam_elem_zero_grad(p.x, m.x, v.x, c);
+        adam_elem_zero_grad(p.y, m.y, v.y, c);
+        adam_elem_zero_grad(p.z, m.z, v.z, c);
+        adam_elem_zero_grad(p.w, m.w, v.w, c);
+        sweep_store(p, W + i); sweep_store(m, M + i); sweep_store(v, V + i);
+      }
     }
     __syncthreads();
     par ^= 1;
@@ -508,13 +541,65 @@ __global__ __launch_bounds__(256) void adam_sweep_tables_kernel(const SweepTable
 // (side == nullptr above) gives them their real update.  Same arithmetic for every row, so the same bits as the parked
 // schedule.  A chunk (256 x ITERS float4) covers (1024 >> sh) whole rows, sh = log2(dim / 4) in [3, 10]: at most 128 rows
 // = 4 words of the bitmap, fetched once per chunk (the chunk index is made wave-uniform first).  The unmarked form above stays
-// what it is: the headline's sweep touches 16 K of 11 M rows and parks them (this kernel with no row marked in its place:
-// P 5.436 -> 5.429 ms, C2 1.086 -> 1.082, i.e. nothing).
-struct SweepTablesMarked {
-  SweepTables t;
-  const unsigned* marks[SWEEP_MAX_TABLES];
-  int sh[SWEEP_MAX_TABLES];
-};
+// what it is for the schedules that park (this kernel with no row marked in its place: P 5.436 -> 5.429 ms, C2 1.086 -> 1.082,
+// i.e. nothing); the headline's steps, 16 K looked-up rows of 11 M, mark theirs too since they are chained (MARKS above).
+// one chunk (chu: wave-uniform), PAIR row triples of a lane in flight at a time
+template <int ITERS, int PAIR>
+__device__ __forceinline__ void sweep_chunk_marked(const SweepTablesMarked& tm, unsigned chu, const AdamConst& c) {
+  int t = 0;
+#pragma unroll
+  for (int q = 1; q < SWEEP_MAX_TABLES; ++q)
+    if (q < tm.t.n && chu >= tm.t.first_chunk[q]) t = q;
+  float4* __restrict__ W = tm.t.W[t];
+  float4* __restrict__ M = tm.t.M[t];
+  float4* __restrict__ V = tm.t.V[t];
+  const int64_t n4 = tm.t.n4[t];
+  const unsigned lc = chu - tm.t.first_chunk[t];
+  const int sh = tm.sh[t];
+  const int64_t r0 = (int64_t)lc * ((256 * ITERS) >> sh);  // first row of the chunk
+  const unsigned* __restrict__ mk = tm.marks[t];
+  unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+  if (mk) {  // (the bitmap is padded by four words)
+    const unsigned* mw = mk + (r0 >> 5);
+    w0 = mw[0]; w1 = mw[1]; w2 = mw[2]; w3 = mw[3];
+  }
+  const int64_t base = (int64_t)lc * (256 * ITERS) + threadIdx.x;
+  // Register budget: the kernels that run NEXT TO this sweep fill the register file -- the encoder's in-projection holds
+  // 2 x 218 (allocated as 2 x 224) of a SIMD's 512 registers, so a CU takes it together with sweep waves of <= 64 registers per SIMD in total, and
+  // the attention backward (2 x 250) with none.  All ITERS loads up front (92 registers) shut the in-projection out of every
+  // CU with a sweep workgroup (651 us instead of 211); one row triple at a time (46) lets ONE sweep wave per SIMD in, so that
+  // a sweep wide enough to finish in time (1.5 workgroups per CU) halved the in-projection's CUs.  PAIR triples in flight per
+  // wave: half as many waves stream as much.
+#pragma unroll
+  for (int k = 0; k < ITERS; k += PAIR) {
+    float4 p[PAIR], m[PAIR], v[PAIR];
+    bool live[PAIR];
+#pragma unroll
+    for (int q = 0; q < PAIR; ++q) {
+      const int64_t i = base + (int64_t)(k + q) * 256;
+      const int64_t row = r0 + (((k + q) * 256 + (int)threadIdx.x) >> sh);
+      const int wj = (int)((row >> 5) - (r0 >> 5));
+      const unsigned word = wj == 0 ? w0 : wj == 1 ? w1 : wj == 2 ? w2 : w3;
+      live[q] = i < n4 && !((word >> (row & 31)) & 1u);
+    }
+#pragma unroll
+    for (int q = 0; q < PAIR; ++q) {
+      const int64_t i = base + (int64_t)(k + q) * 256;
+      if (live[q]) { p[q] = sweep_load(W + i); m[q] = sweep_load(M + i); v[q] = sweep_load(V + i); }
+    }
+#pragma unroll
+    for (int q = 0; q < PAIR; ++q) {
+      const int64_t i = base + (int64_t)(k + q) * 256;
+      if (live[q]) {
+        adam_elem_zero_grad(p[q].x, m[q].x, v[q].x, c);
+        adam_elem_zero_grad(p[q].y, m[q].y, v[q].y, c);
+        adam_elem_zero_grad(p[q].z, m[q].z, v[q].z, c);
+        adam_elem_zero_grad(p[q].w, m[q].w, v[q].w, c);
+        sweep_store(p[q], W + i); sweep_store(m[q], M + i); sweep_store(v[q], V + i);
+      }
+    }
+  }
+}
 template <int ITERS, int PAIR>
 __global__ __launch_bounds__(256) void adam_sweep_tables_marked_kernel(const SweepTablesMarked tm, const double* __restrict__ hyper,
                                                                        unsigned* __restrict__ ctr) {
@@ -527,60 +612,7 @@ __global__ __launch_bounds__(256) void adam_sweep_tables_marked_kernel(const Swe
   int par = 0;
   while (ch < n_chunks) {
     if (threadIdx.x == 0) s_next[par ^ 1] = atomicAdd(&ctr[0], 1u);
-    const unsigned chu = __builtin_amdgcn_readfirstlane(ch);
-    int t = 0;
-#pragma unroll
-    for (int q = 1; q < SWEEP_MAX_TABLES; ++q)
-      if (q < tm.t.n && chu >= tm.t.first_chunk[q]) t = q;
-    float4* __restrict__ W = tm.t.W[t];
-    float4* __restrict__ M = tm.t.M[t];
-    float4* __restrict__ V = tm.t.V[t];
-    const int64_t n4 = tm.t.n4[t];
-    const unsigned lc = chu - tm.t.first_chunk[t];
-    const int sh = tm.sh[t];
-    const int64_t r0 = (int64_t)lc * ((256 * ITERS) >> sh);  // first row of the chunk
-    const unsigned* __restrict__ mk = tm.marks[t];
-    unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-    if (mk) {  // (the bitmap is padded by four words)
-      const unsigned* mw = mk + (r0 >> 5);
-      w0 = mw[0]; w1 = mw[1]; w2 = mw[2]; w3 = mw[3];
-    }
-    const int64_t base = (int64_t)lc * (256 * ITERS) + threadIdx.x;
-    // Register budget: the kernels that run NEXT TO this sweep fill the register file -- the encoder's in-projection holds
-    // 2 x 218 (allocated as 2 x 224) of a SIMD's 512 registers, so a CU takes it together with sweep waves of <= 64 registers per SIMD in total, and
-    // the attention backward (2 x 250) with none.  All ITERS loads up front (92 registers) shut the in-projection out of every
-    // CU with a sweep workgroup (651 us instead of 211); one row triple at a time (46) lets ONE sweep wave per SIMD in, so that
-    // a sweep wide enough to finish in time (1.5 workgroups per CU) halved the in-projection's CUs.  PAIR triples in flight per
-    // wave: half as many waves stream as much.
-#pragma unroll
-    for (int k = 0; k < ITERS; k += PAIR) {
-      float4 p[PAIR], m[PAIR], v[PAIR];
-      bool live[PAIR];
-#pragma unroll
-      for (int q = 0; q < PAIR; ++q) {
-        const int64_t i = base + (int64_t)(k + q) * 256;
-        const int64_t row = r0 + (((k + q) * 256 + (int)threadIdx.x) >> sh);
-        const int wj = (int)((row >> 5) - (r0 >> 5));
-        const unsigned word = wj == 0 ? w0 : wj == 1 ? w1 : wj == 2 ? w2 : w3;
-        live[q] = i < n4 && !((word >> (row & 31)) & 1u);
-      }
-#pragma unroll
-      for (int q = 0; q < PAIR; ++q) {
-        const int64_t i = base + (int64_t)(k + q) * 256;
-        if (live[q]) { p[q] = sweep_load(W + i); m[q] = sweep_load(M + i); v[q] = sweep_load(V + i); }
-      }
-#pragma unroll
-      for (int q = 0; q < PAIR; ++q) {
-        const int64_t i = base + (int64_t)(k + q) * 256;
-        if (live[q]) {
-          adam_elem_zero_grad(p[q].x, m[q].x, v[q].x, c);
-          adam_elem_zero_grad(p[q].y, m[q].y, v[q].y, c);
-          adam_elem_zero_grad(p[q].z, m[q].z, v[q].z, c);
-          adam_elem_zero_grad(p[q].w, m[q].w, v[q].w, c);
-          sweep_store(p[q], W + i); sweep_store(m[q], M + i); sweep_store(v[q], V + i);
-        }
-      }
-    }
+    sweep_chunk_marked<ITERS, PAIR>(tm, __builtin_amdgcn_readfirstlane(ch), c);
     __syncthreads();
     par ^= 1;
     ch = s_next[par];
@@ -600,6 +632,31 @@ __global__ __launch_bounds__(256) void adam_mark_rows_kernel(const int64_t* __re
   if (i >= n_ids) return;
   const int64_t row = ids[i];
   if (row >= 0 && row < n_rows) atomicOr(&marks[row >> 5], 1u << (row & 31));  // ids of another rank's rows / invalid ids: nothing
+}
+
+// The launch between two chained sweeps (tt_adam_mark_advance): every table's rows of the NEXT step marked in bitmaps the
+// caller has cleared, and the step constants advanced (last workgroup; nothing here reads them) -- the gap between the
+// sweeps is this one launch.
+struct MarkJobs {
+  const int64_t* ids[SWEEP_MAX_TABLES_DECL];
+  int64_t n_ids[SWEEP_MAX_TABLES_DECL], n_rows[SWEEP_MAX_TABLES_DECL];
+  unsigned* marks[SWEEP_MAX_TABLES_DECL];
+  unsigned first_block[SWEEP_MAX_TABLES_DECL + 1];
+  int n;
+};
+__global__ __launch_bounds__(256) void adam_mark_advance_kernel(const MarkJobs jobs, double* h) {
+  if (blockIdx.x == jobs.first_block[jobs.n]) {
+    if (threadIdx.x == 0) advance_step(h, nullptr, 0);
+    return;
+  }
+  int t = 0;
+#pragma unroll
+  for (int q = 1; q < SWEEP_MAX_TABLES_DECL; ++q)
+    if (q < jobs.n && blockIdx.x >= jobs.first_block[q]) t = q;
+  const int64_t i = (int64_t)(blockIdx.x - jobs.first_block[t]) * 256 + threadIdx.x;
+  if (i >= jobs.n_ids[t]) return;
+  const int64_t row = jobs.ids[t][i];
+  if (row >= 0 && row < jobs.n_rows[t]) atomicOr(&jobs.marks[t][row >> 5], 1u << (row & 31));
 }
 
 __global__ __launch_bounds__(256) void adam_sweep_scalar_kernel(float* __restrict__ W, float* __restrict__ M,
@@ -1015,11 +1072,11 @@ extern "C" int tt_adam_marked_supported(int64_t dim) {
   return 1;
 }
 
-extern "C" int tt_adam_tables_sweep_marked(const tt_adam_tensor* tables, const int64_t* dims, const uint32_t* const* marks,
-                                           int32_t n_tables, const double* hyper, int32_t n_wgs, tt_stream_t stream) {
+// the tables of a marked sweep into the kernels' descriptor; -> 0 or the error code (message set)
+static int fill_marked_tables(const tt_adam_tensor* tables, const int64_t* dims, const uint32_t* const* marks, int32_t n_tables,
+                              const double* hyper, SweepTablesMarked& tm) {
   if (!tables || !dims || !marks || !hyper) return fail_arg("tt_adam_tables_sweep_marked: null pointer");
   if (n_tables <= 0 || n_tables > SWEEP_MAX_TABLES) return fail_arg("tt_adam_tables_sweep_marked: 1..4 tables");
-  SweepTablesMarked tm{};
   unsigned chunks = 0;
   for (int t = 0; t < n_tables; ++t) {
     const tt_adam_tensor& d = tables[t];
@@ -1031,7 +1088,7 @@ extern "C" int tt_adam_tables_sweep_marked(const tt_adam_tensor* tables, const i
     tm.t.n4[t] = d.n / 4;
     tm.t.first_chunk[t] = chunks;
     const int64_t c = ceil_div(d.n / 4, 256 * 4);
-    if (c + chunks >= (1ll << 32)) return fail_arg("tt_adam_tables_sweep_marked: too many chunks");
+    if (c + chunks >= (1ll << 32) - 1) return fail_arg("tt_adam_tables_sweep_marked: too many chunks");
     chunks += (unsigned)c;
     tm.marks[t] = marks[t];  // NULL: no row of this table is marked
     int sh = 0;
@@ -1040,17 +1097,72 @@ extern "C" int tt_adam_tables_sweep_marked(const tt_adam_tensor* tables, const i
   }
   tm.t.first_chunk[n_tables] = chunks;
   tm.t.n = n_tables;
+  return 0;
+}
+
+static unsigned sweep_grid(int32_t n_wgs) {
   static const int wgs_env = getenv("TT_SWEEP_WGS") ? atoi(getenv("TT_SWEEP_WGS")) : 0;
   const int want = getenv("TT_SWEEP_WGS") ? wgs_env : n_wgs;
-  unsigned* ctr = reinterpret_cast<unsigned*>(const_cast<double*>(hyper) + 7);
   unsigned grid = (unsigned)(device_cu_count() * SWEEP_DEFAULT_PERSIST);
   if (want > 0 && (unsigned)want < grid) grid = (unsigned)want;
+  return grid;
+}
+
+extern "C" int tt_adam_tables_sweep_marked(const tt_adam_tensor* tables, const int64_t* dims, const uint32_t* const* marks,
+                                           int32_t n_tables, const double* hyper, int32_t n_wgs, tt_stream_t stream) {
+  SweepTablesMarked tm{};
+  int rc = fill_marked_tables(tables, dims, marks, n_tables, hyper, tm);
+  if (rc) return rc;
+  unsigned* ctr = reinterpret_cast<unsigned*>(const_cast<double*>(hyper) + 7);
+  const unsigned grid = sweep_grid(n_wgs);
   hipStream_t st = S(stream);
   ProfScope prof("adam_sweep_kernel", st);
   // two row triples in flight per wave: 62 registers (see the kernel); one at a time (46) 3.27 ms per C3 step at its best
   // width (384 workgroups), two 3.09 (256), four (92 registers) 3.34 (128) -- one process each, profiles/r06_marked_sweep_AB.txt
   adam_sweep_tables_marked_kernel<4, 2><<<grid, 256, 0, st>>>(tm, hyper, ctr);
   return check_launch("adam_sweep_tables_marked_kernel");
+}
+
+extern "C" int tt_adam_tables_sweep_chained(const tt_adam_tensor* tables, const int64_t* dims, const uint32_t* const* marks,
+                                            int32_t n_tables, const double* hyper, int32_t n_wgs, int32_t alone_wgs,
+                                            const uint32_t* alone_flag, uint32_t tag, tt_stream_t stream) {
+  SweepTablesChained a{};
+  int rc = fill_marked_tables(tables, dims, marks, n_tables, hyper, a.m);
+  if (rc) return rc;
+  unsigned* ctr = reinterpret_cast<unsigned*>(const_cast<double*>(hyper) + 7);
+  const unsigned grid = sweep_grid(n_wgs);
+  const bool thin = alone_flag && alone_wgs > 0 && (unsigned)alone_wgs < grid;
+  a.alone_flag = thin ? alone_flag : nullptr;
+  a.tag = tag;
+  a.alone_wgs = thin ? (unsigned)alone_wgs : grid;
+  hipStream_t st = S(stream);
+  ProfScope prof("adam_sweep_kernel", st);
+  // Two row triples in flight, like the held sweep: 62 registers.  The unmarked kernel holds 44 (its early-out keeps the
+  // loads from being hoisted: it never had all four triples in flight either); all four here are 92, and three such waves
+  // per SIMD (276 of 512 registers) leave no room for the 256-register forward / backward workgroups the persistent form
+  // exists to let in (see launch_sweep) -- profiles/chained_sweep_resources.txt
+  adam_sweep_tables_kernel<4, 2, true><<<grid, 256, 0, st>>>(a, hyper, ctr);
+  return check_launch("adam_sweep_tables_kernel");
+}
+
+extern "C" int tt_adam_mark_advance(double* hyper, const tt_adam_mark_job* jobs, int32_t n_jobs, tt_stream_t stream) {
+  if (!hyper || (n_jobs > 0 && !jobs)) return fail_arg("tt_adam_mark_advance: null pointer");
+  if (n_jobs < 0 || n_jobs > SWEEP_MAX_TABLES) return fail_arg("tt_adam_mark_advance: 0..4 tables");
+  MarkJobs a{};
+  a.n = n_jobs;
+  unsigned blocks = 0;
+  for (int i = 0; i < n_jobs; ++i) {
+    const tt_adam_mark_job& j = jobs[i];
+    if (!j.ids || !j.marks) return fail_arg("tt_adam_mark_advance: null pointer");
+    if (j.n_ids <= 0 || j.n_rows <= 0 || ceil_div(j.n_ids, 256) + blocks >= (1ll << 31)) return fail_arg("tt_adam_mark_advance: sizes");
+    if (j.marks_words < tt_adam_marks_words(j.n_rows)) { set_error("tt_adam_mark_advance: bitmap of %lld words < %lld", (long long)j.marks_words, (long long)tt_adam_marks_words(j.n_rows)); return TT_E_WORKSPACE; }
+    a.ids[i] = j.ids; a.n_ids[i] = j.n_ids; a.n_rows[i] = j.n_rows; a.marks[i] = j.marks;
+    a.first_block[i] = blocks;
+    blocks += (unsigned)ceil_div(j.n_ids, 256);
+  }
+  for (int i = n_jobs; i <= SWEEP_MAX_TABLES; ++i) a.first_block[i] = blocks;
+  adam_mark_advance_kernel<<<blocks + 1, 256, 0, S(stream)>>>(a, hyper);
+  return check_launch("adam_mark_advance_kernel");
 }
 
 // A HIP stream of the device's LEAST priority for the sweep: the backward kernels on the

@@ -37,7 +37,10 @@ parks the old rows straight from the id lists (no sort needed yet), starts the s
 hands the lookups a view of the parked rows (``ops.ActiveStash``), so the id sort, forward AND
 backward all run under the sweep.  It assumes every
 ``train_forward`` executed with autograd enabled is followed by ``backward()`` and ``step()``
-(exactly the reference loop); results are again bit-identical to the serial schedule.
+(exactly the reference loop); results are again bit-identical to the serial schedule.  Steps that look up few rows are
+CHAINED there (``_launch_chained``): their rows are marked for the sweep to step over instead of parked, so the finish does
+not wait for the sweep, the next step's sweep follows on the sweep's stream behind one launch, and the sweep thins itself
+once the main stream has run dry.  ``step()`` still ends with the caller's stream waiting for the sweep.
 
 Deferred schedule (``lazy=True``; SURVEY 8f-3, reported separately from the dense figure).  The
 zero-gradient steps of an untouched row are a recurrence on the row alone, so instead of sweeping
@@ -157,6 +160,14 @@ class DenseExactAdam(torch.optim.Optimizer):
         self._sweep_pending_marked = False
         self._sweep_events = None  # keep_sweep_events(): (start, end) event pairs of the table sweep launches
         self._catchup_last: Dict[int, tuple] = {}  # deferred schedule: table -> (event, stream) of its latest catch-up this step
+        # chained steps (_launch_chained): nothing but events and the two bitmaps per table carries over between steps
+        self._chained = False  # the step in flight is a chained one
+        self._chain_last_done: Optional[torch.cuda.Event] = None  # the previous step's sweep_done, if that step was chained
+        self._chain_main_done = None  # (event, stream) behind the last main-stream reader of a step's constants
+        self._chain_cleared = None  # (step, stream): that step's bitmaps were cleared on that stream by the step before it
+        self._chain_marks: Dict[tuple, torch.Tensor] = {}  # (table, step parity) -> bitmap
+        self._alone_flag: Optional[torch.Tensor] = None  # the device word a chained sweep thins itself on
+        self._alone_tag: Optional[int] = None  # ... and what step() writes there (None: this step's sweep does not thin)
 
     # state is created lazily, on the parameters' device
     def _init_state(self) -> None:
@@ -372,6 +383,7 @@ class DenseExactAdam(torch.optim.Optimizer):
             raise ValueError("DenseExactAdam needs one common step count for all parameters")
         self._resume_step = self._sweep_ctl.resume_step = steps.pop() if steps else 0
         self._begun = None
+        self._chained, self._chain_last_done = False, None
         self._ready = False  # device-side state is rebuilt around the loaded moments
 
     def _advance_lazy(self) -> None:
@@ -413,17 +425,6 @@ class DenseExactAdam(torch.optim.Optimizer):
             self._init_state()
         hyper = self._hyper.data_ptr()
         capturing = torch.cuda.is_current_stream_capturing()  # whole-step hipGraph: no timing events, no controller
-        ev_begin = None
-        if capturing:
-            self._sweep_ctl.record = None
-        else:
-            self._tune_sweep()
-            ev_begin = torch.cuda.Event(enable_timing=True)
-            ev_begin.record()
-            self._sweep_ctl.began(ev_begin, self._host_steps + 1)
-        if announced is None:
-            N.check(lib.tt_adam_advance(hyper, N.stream()), "tt_adam_advance")
-        self._host_steps += 1
         begun: Dict[torch.nn.Parameter, _TableStep] = {}
         stash_jobs = []  # forward mode: the step-count advance and every table's stash go out as ONE launch
         todo = []  # (table, id blocks, rows it owns)
@@ -445,9 +446,32 @@ class DenseExactAdam(torch.optim.Optimizer):
         # ... and nothing is parked at all where the sweep can step over the looked-up rows instead (a bitmap of the step's
         # rows, tt_adam_mark_rows): no gather in front of the sweep, no sweep traffic for rows the finish overwrites; the
         # lookups read the table, whose marked rows keep their old values until the finish, and the finish reads p, m, v there
-        marked = (split_planes and _MARK_ROWS and all(lib.tt_adam_marked_supported(p.shape[1]) for p, _, _ in todo)
-                  and all((p.data_ptr() | self.state[p]["exp_avg"].data_ptr() | self.state[p]["exp_avg_sq"].data_ptr()) % 16 == 0
-                          for p, _, _ in todo))
+        markable = (announced is not None and not capturing and 0 < len(todo) <= 4 and _MARK_ROWS
+                    and all(lib.tt_adam_marked_supported(p.shape[1]) for p, _, _ in todo)
+                    and all((p.data_ptr() | self.state[p]["exp_avg"].data_ptr() | self.state[p]["exp_avg_sq"].data_ptr()) % 16 == 0
+                            for p, _, _ in todo))
+        held = announced is not None and not capturing and ((n_stashed >= 65536 and not self._sharded) or hold_sweep)
+        # ... and where the sweep is not held back either (few looked-up rows, the base model's steps), marking the rows takes
+        # the step's two ends off the sweep's stream altogether: CHAINED steps (_launch_chained)
+        chained = (markable and not held and not self._sharded and self.overlap_sweep == "forward"
+                   and os.environ.get("TT_ADAM_CHAIN", "1") != "0")
+        marked = chained or (split_planes and markable)
+        self._chained = chained
+        if not chained:
+            self._chain_last_done = None
+        if capturing:
+            self._sweep_ctl.record = None
+        else:
+            self._tune_sweep()
+            # a chained step's period runs from the previous sweep's end to its own sweep's end: that IS the step there
+            ev_begin = self._chain_last_done
+            if ev_begin is None:
+                ev_begin = torch.cuda.Event(enable_timing=True)
+                ev_begin.record()
+            self._sweep_ctl.began(ev_begin, self._host_steps + 1)
+        if announced is None:
+            N.check(lib.tt_adam_advance(hyper, N.stream()), "tt_adam_advance")
+        self._host_steps += 1
         for p, blocks, n_rows in todo:
             dim = p.shape[1]
             shard = getattr(p, "_tt_shard", None)
@@ -471,6 +495,9 @@ class DenseExactAdam(torch.optim.Optimizer):
                                                 plan.seg_begin.data_ptr(), plan.n_unique.data_ptr(), side.data_ptr(),
                                                 side.numel(), N.stream()), "tt_adam_table_stash")
             begun[p] = _TableStep(plan, side, announced is not None, marked, n_rows)
+        if chained:
+            self._launch_chained(begun)
+            return
         if marked:
             N.check(lib.tt_adam_advance(hyper, N.stream()), "tt_adam_advance")
         elif announced is not None:
@@ -541,12 +568,11 @@ class DenseExactAdam(torch.optim.Optimizer):
         # profile), on the critical path.  The gather's Function calls release_sweep() once it is queued; zero_grad() /
         # step() do if nobody did.  The sweep is a third of such a step: starting it 0.1 ms later costs nothing.
         self._sweep_done = None
-        n_announced = sum(ts.plan.n for ts in begun.values()) if announced is not None else 0
         # ... and a caller whose logits kernels ARE the step (row-sharded tables from W = 4: thin row blocks, W*B negatives
         # per user) asks for the sweep to start with the BACKWARD logits kernel (zero_grad() releases it): the forward
         # logits kernel then runs at 0.81 instead of 0.73 of the matrix pipe, the backward one -- which streams the kept
         # logits from HBM anyway -- loses less than that (round 4: 4.10 vs 4.26 ms per emulated W = 8 step)
-        if _HOLD_SWEEP and announced is not None and not capturing and ((n_announced >= 65536 and not self._sharded) or hold_sweep):
+        if _HOLD_SWEEP and held:
             self._sweep_pending = launch_sweep
             self._sweep_pending_marked = marked
             # hold_sweep: until the BACKWARD logits kernel is in the main stream's queue (ops.InBatchSoftmaxCE.backward
@@ -569,6 +595,69 @@ class DenseExactAdam(torch.optim.Optimizer):
         self._plan_done = None
         self._plans_pending = announced is not None and bool(begun)
         self._plan_ready = ready if self._plans_pending else None
+        self._begun = begun
+
+    def _launch_chained(self, begun: Dict[torch.nn.Parameter, _TableStep]) -> None:
+        """The chained step's begin.  Its rows are marked, so the finish needs nothing from the sweep and the sweep nothing
+        from a stash: on the sweep's stream the order is
+            sweep(n) -> [main_done(n), ids(n+1), cleared bitmaps] -> mark + advance to n+1 (ONE launch) -> sweep(n+1)
+        and the main stream waits for the advance before anything reads the step constants.  The bitmaps alternate between
+        two per table; step() clears the next step's once the main stream has run dry (the sweep that last read them ended
+        a step ago), so the sweep's stream waits for ONE event here.
+        What this step's id lists wait for on the caller's stream is what this step waits for -- step() ends with the
+        caller's stream waiting for the sweep, so whatever follows a step sees complete tables."""
+        lib = N.load()
+        hyper = self._hyper.data_ptr()
+        main, side = torch.cuda.current_stream(), self._side_stream
+        dev = next(iter(begun)).device
+        parity = self._host_steps & 1
+        jobs = (N.AdamMarkJob * len(begun))()
+        mark_ptrs = (C.c_void_p * len(begun))()
+        for i, (p, ts) in enumerate(begun.items()):
+            words = lib.tt_adam_marks_words(ts.n_rows)
+            bm = self._chain_marks.get((id(p), parity))
+            if bm is None or bm.numel() < words:
+                bm = self._chain_marks[(id(p), parity)] = torch.zeros(words, dtype=torch.int32, device=dev)
+            elif self._chain_cleared != (self._host_steps, main):
+                bm.zero_()  # (the step before this one was not a chained one on this stream: nobody cleared them, see step())
+            j = jobs[i]
+            j.ids, j.n_ids, j.n_rows, j.marks, j.marks_words = ts.plan.ids.data_ptr(), ts.plan.n, ts.n_rows, bm.data_ptr(), bm.numel()
+            mark_ptrs[i] = bm.data_ptr()
+        ready = torch.cuda.Event()
+        ready.record(main)  # the id lists exist, the bitmaps are clear, the previous step's constants have had their last reader
+        if self._chain_main_done is not None and self._chain_main_done[1] != main:
+            side.wait_event(self._chain_main_done[0])
+        side.wait_event(ready)
+        N.check(lib.tt_adam_mark_advance(hyper, jobs, len(begun), side.cuda_stream), "tt_adam_mark_advance")
+        advanced = ev_s0 = torch.cuda.Event(enable_timing=True)  # (also the sweep launch's start for the controller: one record)
+        advanced.record(side)
+        main.wait_event(advanced)
+        descs = (N.AdamTensor * len(begun))()
+        for i, p in enumerate(begun):
+            st = self.state[p]
+            descs[i].p, descs[i].g, descs[i].m, descs[i].v = p.data_ptr(), None, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+            descs[i].n = p.numel()
+        dims = (C.c_int64 * len(begun))(*[p.shape[1] for p in begun])
+        # once the main stream has run dry (step() writes the step number into the word) the sweep is alone on the chip,
+        # where 2 workgroups per CU stream faster than the 3 that share it best
+        alone = os.environ.get("TT_SWEEP_ALONE_WGS")
+        alone = int(alone) if alone is not None else 2 * torch.cuda.get_device_properties(dev).multi_processor_count
+        if self._alone_flag is None:
+            self._alone_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._alone_tag = (self._host_steps & 0x7FFFFFFF) if alone > 0 else None
+        N.check(lib.tt_adam_tables_sweep_chained(descs, dims, mark_ptrs, len(begun), hyper, self._sweep_wgs, max(alone, 0),
+                                                 self._alone_flag.data_ptr(), self._alone_tag or 0, side.cuda_stream),
+                "tt_adam_tables_sweep_chained")
+        self._sweep_done = torch.cuda.Event(enable_timing=True)
+        self._sweep_done.record(side)
+        self._chain_last_done = self._sweep_done
+        self._sweep_ctl.swept(ev_s0, self._sweep_done)
+        if self._sweep_events is not None and len(self._sweep_events) < 65536:
+            self._sweep_events.append((ev_s0, self._sweep_done))
+        self._sweep_pending = None
+        self._plan_done = None
+        self._plans_pending = True
+        self._plan_ready = ready
         self._begun = begun
 
     def keep_sweep_events(self, on: bool = True) -> None:
@@ -743,6 +832,7 @@ class DenseExactAdam(torch.optim.Optimizer):
             raise NotImplementedError("closure is not supported")
         if not self._ready:
             self._init_state()
+        chained = False
         lib = N.load()
         hyper = self._hyper.data_ptr()
         if self._sharded and self._begun is None:  # (checked BEFORE any collective is started)
@@ -753,7 +843,9 @@ class DenseExactAdam(torch.optim.Optimizer):
         if self._begun is not None:
             # overlapped schedule: hyper already advanced, tables already swept on the side stream
             self._launch_plans(side=False)  # nobody called zero_grad() after the forward: sort now, in line
-            torch.cuda.current_stream().wait_event(self._sweep_done)
+            chained = self._chained
+            if not chained:  # (a chained step's rows are marked: its finish neither reads nor writes what the sweep touches)
+                torch.cuda.current_stream().wait_event(self._sweep_done)
             if self._plan_done is not None:
                 torch.cuda.current_stream().wait_event(self._plan_done)
                 self._plan_done = None
@@ -773,8 +865,9 @@ class DenseExactAdam(torch.optim.Optimizer):
                 N.check(lib.tt_adam_tables_finish(jobs, len(self._begun), hyper, N.stream()), "tt_adam_tables_finish")
             self._begun = None
             if self._sweep_ctl.record is not None:
-                end = torch.cuda.Event(enable_timing=True)
-                end.record()
+                end = self._sweep_done if chained else torch.cuda.Event(enable_timing=True)
+                if not chained:
+                    end.record()
                 self._sweep_ctl.ended(end)
         elif self.lazy:
             if self._prefetch_done is not None:  # rows being replayed for a later batch: finish first
@@ -848,4 +941,19 @@ class DenseExactAdam(torch.optim.Optimizer):
                 descs[i].m, descs[i].v = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
                 descs[i].n = p.numel()
             N.check(lib.tt_adam_dense(descs, len(live), hyper, N.stream()), "tt_adam_dense")
+        if chained:
+            # the step constants have had their last reader on this stream: the sweep's stream may advance them (next begin);
+            # nothing is left to run beside the sweep: it may thin itself; and what the caller enqueues next sees swept tables
+            main = torch.cuda.current_stream()
+            for (_, parity), bm in self._chain_marks.items():
+                if parity == (self._host_steps + 1) & 1:
+                    bm.zero_()  # the next step's bitmaps: last read by the sweep of the step before this one
+            self._chain_cleared = (self._host_steps + 1, main)
+            done = torch.cuda.Event()
+            done.record(main)
+            self._chain_main_done = (done, main)
+            if self._alone_tag is not None:
+                self._alone_flag.fill_(self._alone_tag)
+            main.wait_event(self._sweep_done)
+            self._chained = False
         return None
