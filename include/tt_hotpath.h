@@ -338,7 +338,11 @@ int tt_debias_loss_bwd(int mode, const float* grad_loss, const float* row_ce, in
  * the sorted order; seg_begin[n_unique] == n), n_unique int32[1].
  * Sentinel rows: tt_adam_table / _stash / _finish ignore runs whose row id is >= the
  * n_rows THEY are given, so a caller may plan with n_rows+1 and map "not my row" ids to
- * n_rows (the sharded trainer does, after all-gathering every rank's ids). */
+ * n_rows (the sharded trainer does, after all-gathering every rank's ids).
+ * tt_rowgrad_dense is NOT one of them: it takes no n_rows and writes the row of EVERY run, so the plan
+ * given to it must be built with the dense buffer's own n_rows (no sentinel rows; an out-of-range id is
+ * row 0 in such a plan, with the plan's flag raised).  It overwrites the rows the plan names and touches
+ * no other row.  Id lists hold fewer than 2^31 ids (the plan is int32). */
 int64_t tt_rowgrad_workspace_bytes(int64_t n_ids);
 int tt_rowgrad_plan(const int64_t* ids, int64_t n_ids, int64_t n_rows, int32_t* sorted_ids,
                     int32_t* perm, int32_t* seg_begin, int32_t* n_unique, int32_t* oob_flag,
@@ -675,7 +679,8 @@ int tt_enc_last_fwd_len(const float* x, int64_t B, int64_t H, int64_t D, int64_t
  *                     slot in which the row of the caller's i-th id comes back; src_of[slot] = i (-1 = padding):
  *                     the backward sends gradient row src_of[slot] in that slot.  A bucket larger than cap sets
  *                     *overflow_flag and slot_of = -1 for the ids that did not fit (cannot happen when cap
- *                     comes from the all-reduced count).  world <= 1024.
+ *                     comes from the all-reduced count).  world <= 1024; fewer than 2^31 ids per list (the
+ *                     counts are int32).
  *   tt_route_localize owner side: local[i] = ids[i] - lo for lo <= ids[i] < lo + n_local, else the
  *                     sentinel n_local (padding, foreign ids): tt_gather_rows then yields a zero row and
  *                     the Adam kernels skip the run. */

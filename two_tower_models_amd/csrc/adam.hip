@@ -1414,8 +1414,9 @@ extern "C" int tt_rowgrad_dense(const tt_grad_sources* src, int64_t n_ids, int64
                                 const int32_t* perm, const int32_t* seg_begin, const int32_t* n_unique,
                                 float* dense_grad, tt_stream_t stream) {
   if (!sorted_ids || !perm || !seg_begin || !n_unique || !dense_grad) return fail_arg("tt_rowgrad_dense: null pointer");
-  if (n_ids <= 0 || dim <= 0) return fail_arg("tt_rowgrad_dense: sizes");
+  if (n_ids <= 0 || n_ids >= ((int64_t)1 << 31) || dim <= 0) return fail_arg("tt_rowgrad_dense: sizes");  // int32 plan
   if (!check_sources(src, n_ids, dim)) return fail_arg("tt_rowgrad_dense: gradient sources");
+  ProfScope prof("rowgrad_dense_kernel", S(stream));
   rowgrad_dense_kernel<<<(unsigned)ceil_div(n_ids, 4), 256, 0, S(stream)>>>(*src, INT64_MAX, dim, sorted_ids, perm, seg_begin, n_unique, dense_grad);
   return check_launch("rowgrad_dense_kernel");
 }

@@ -129,6 +129,7 @@ __global__ __launch_bounds__(256) void route_localize_kernel(const int64_t* __re
 }
 
 constexpr int32_t ROUTE_MAX_WORLD = 1024;  // 16 x world x 4 B of LDS in route_build_kernel (64 KiB)
+// lists of fewer than 2^31 ids: counts, *max_count and the per-tile offsets are int32
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The same three stages for ALL lookups of a step at once (tt_route_*_jobs): a step of the base model routes two id lists
@@ -307,15 +308,19 @@ extern "C" int tt_route_count(const int64_t* ids, int64_t n_ids, int64_t n_rows,
                               int32_t* counts, int32_t* max_count, int32_t* oob_flag, void* ws, int64_t ws_bytes,
                               tt_stream_t stream) {
   if (!ids || !counts || !max_count || !ws) return fail_arg("tt_route_count: null pointer");
-  if (n_ids <= 0 || n_rows <= 0 || rows_per_rank <= 0 || world <= 0 || world > ROUTE_MAX_WORLD)
+  if (n_ids <= 0 || n_ids >= ((int64_t)1 << 31) || n_rows <= 0 || rows_per_rank <= 0 || world <= 0 || world > ROUTE_MAX_WORLD)
     return fail_arg("tt_route_count: sizes");
   if (ws_bytes < tt_route_workspace_bytes(n_ids, world)) { set_error("tt_route_count: workspace"); return TT_E_WORKSPACE; }
   hipStream_t st = S(stream);
   const int64_t tiles = ceil_div(n_ids, RT);
   int32_t* hist = reinterpret_cast<int32_t*>(ws);
-  route_hist_kernel<<<(unsigned)tiles, RT, world * sizeof(int32_t), st>>>(ids, n_ids, n_rows, rows_per_rank, world, hist, oob_flag);
-  int rc = check_launch("route_hist_kernel");
-  if (rc) return rc;
+  int rc;
+  {
+    ProfScope prof("route_hist_kernel", st);
+    route_hist_kernel<<<(unsigned)tiles, RT, world * sizeof(int32_t), st>>>(ids, n_ids, n_rows, rows_per_rank, world, hist, oob_flag);
+    if ((rc = check_launch("route_hist_kernel"))) return rc;
+  }
+  ProfScope prof("route_scan_kernel", st);
   route_scan_kernel<<<1, 256, 0, st>>>(hist, tiles, world, counts, max_count);
   return check_launch("route_scan_kernel");
 }
@@ -324,14 +329,18 @@ extern "C" int tt_route_build(const int64_t* ids, int64_t n_ids, int64_t n_rows,
                               int64_t cap, const void* ws, int64_t ws_bytes, int64_t* send_ids, int64_t* slot_of,
                               int64_t* src_of, int32_t* overflow_flag, tt_stream_t stream) {
   if (!ids || !ws || !send_ids || !slot_of || !src_of || !overflow_flag) return fail_arg("tt_route_build: null pointer");
-  if (n_ids <= 0 || n_rows <= 0 || rows_per_rank <= 0 || world <= 0 || world > ROUTE_MAX_WORLD || cap <= 0)
+  if (n_ids <= 0 || n_ids >= ((int64_t)1 << 31) || n_rows <= 0 || rows_per_rank <= 0 || world <= 0 || world > ROUTE_MAX_WORLD || cap <= 0)
     return fail_arg("tt_route_build: sizes");
   if (ws_bytes < tt_route_workspace_bytes(n_ids, world)) { set_error("tt_route_build: workspace"); return TT_E_WORKSPACE; }
   hipStream_t st = S(stream);
   const int64_t n_slots = (int64_t)world * cap;
-  route_fill_kernel<<<(unsigned)ceil_div(n_slots, 256), 256, 0, st>>>(send_ids, src_of, n_slots);
-  int rc = check_launch("route_fill_kernel");
-  if (rc) return rc;
+  int rc;
+  {
+    ProfScope prof("route_fill_kernel", st);
+    route_fill_kernel<<<(unsigned)ceil_div(n_slots, 256), 256, 0, st>>>(send_ids, src_of, n_slots);
+    if ((rc = check_launch("route_fill_kernel"))) return rc;
+  }
+  ProfScope prof("route_build_kernel", st);
   route_build_kernel<<<(unsigned)ceil_div(n_ids, RT), RT, 16 * world * sizeof(int32_t), st>>>(
       ids, n_ids, n_rows, rows_per_rank, world, cap, reinterpret_cast<const int32_t*>(ws), send_ids, slot_of, src_of,
       overflow_flag);
@@ -342,6 +351,7 @@ extern "C" int tt_route_localize(const int64_t* ids, int64_t n_ids, int64_t lo, 
                                  tt_stream_t stream) {
   if (!ids || !local) return fail_arg("tt_route_localize: null pointer");
   if (n_ids <= 0 || lo < 0 || n_local < 0) return fail_arg("tt_route_localize: sizes");
+  ProfScope prof("route_localize_kernel", S(stream));
   route_localize_kernel<<<(unsigned)ceil_div(n_ids, 256), 256, 0, S(stream)>>>(ids, n_ids, lo, n_local, local);
   return check_launch("route_localize_kernel");
 }
@@ -355,7 +365,7 @@ static int fill_jobs(const tt_route_job* jobs, int32_t n_jobs, int32_t world, bo
   for (int j = 0; j < n_jobs; ++j) {
     const tt_route_job& q = jobs[j];
     if (!q.ids || !q.counts || !q.max_count || !q.ws) return fail_arg(who);
-    if (q.n_ids <= 0 || q.n_rows <= 0 || q.rows_per_rank <= 0) return fail_arg(who);
+    if (q.n_ids <= 0 || q.n_ids >= ((int64_t)1 << 31) || q.n_rows <= 0 || q.rows_per_rank <= 0) return fail_arg(who);
     if (q.ws_bytes < tt_route_workspace_bytes(q.n_ids, world)) { set_error("%s: workspace", who); return TT_E_WORKSPACE; }
     if (build && (!q.send_ids || !q.slot_of || !q.src_of || q.cap <= 0)) return fail_arg(who);
     a.ids[j] = q.ids; a.n_ids[j] = q.n_ids; a.n_rows[j] = q.n_rows; a.rows_per_rank[j] = q.rows_per_rank; a.cap[j] = q.cap;
@@ -375,9 +385,12 @@ extern "C" int tt_route_count_jobs(const tt_route_job* jobs, int32_t n_jobs, int
   int rc = fill_jobs(jobs, n_jobs, world, false, a, "tt_route_count_jobs");
   if (rc) return rc;
   hipStream_t st = S(stream);
-  route_hist_jobs_kernel<<<a.first_block[n_jobs], RT, world * sizeof(int32_t), st>>>(a, world, oob_flag);
-  rc = check_launch("route_hist_jobs_kernel");
-  if (rc) return rc;
+  {
+    ProfScope prof("route_hist_jobs_kernel", st);
+    route_hist_jobs_kernel<<<a.first_block[n_jobs], RT, world * sizeof(int32_t), st>>>(a, world, oob_flag);
+    if ((rc = check_launch("route_hist_jobs_kernel"))) return rc;
+  }
+  ProfScope prof("route_scan_jobs_kernel", st);
   route_scan_jobs_kernel<<<(unsigned)n_jobs, 256, 0, st>>>(a, world);
   return check_launch("route_scan_jobs_kernel");
 }
@@ -388,6 +401,7 @@ extern "C" int tt_route_build_jobs(const tt_route_job* jobs, int32_t n_jobs, int
   RouteJobs a{};
   int rc = fill_jobs(jobs, n_jobs, world, true, a, "tt_route_build_jobs");
   if (rc) return rc;
+  ProfScope prof("route_build_jobs_kernel", S(stream));
   route_build_jobs_kernel<<<a.first_block[n_jobs], RT, 16 * world * sizeof(int32_t), S(stream)>>>(a, world, overflow_flag);
   return check_launch("route_build_jobs_kernel");
 }
@@ -411,6 +425,7 @@ extern "C" int tt_route_serve_jobs(const tt_route_serve_job* jobs, int32_t n_job
     blocks += (unsigned)ceil_div(q.n_ids, 8);
   }
   for (int j = n_jobs; j <= TT_ROUTE_MAX_JOBS; ++j) a.first_block[j] = blocks;
+  ProfScope prof("route_serve_jobs_kernel", S(stream));
   route_serve_jobs_kernel<<<blocks, 256, 0, S(stream)>>>(a);
   return check_launch("route_serve_jobs_kernel");
 }

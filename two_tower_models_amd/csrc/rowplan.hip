@@ -391,6 +391,7 @@ extern "C" int tt_rowgrad_plan(const int64_t* ids, int64_t n_ids, int64_t n_rows
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) { set_error("plan_small_kernel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
     }
+    ProfScope prof("plan_small_kernel", st);
     plan_small_kernel<<<1, PS_THREADS, lds, st>>>(ids, (int)n_ids, n_rows, kpt, n_rows > 1 ? (bits + 3) / 4 : 0, sorted_ids, perm,
                                                   seg_begin, n_unique, oob_flag);
     return check_launch("plan_small_kernel");
@@ -409,23 +410,42 @@ extern "C" int tt_rowgrad_plan(const int64_t* ids, int64_t n_ids, int64_t n_rows
   int32_t* kbuf[2] = {sorted_ids, tkeys};
   int32_t* vbuf[2] = {perm, tvals};
   int cur = (passes % 2 == 0) ? 0 : 1;
-  plan_init_kernel<<<(unsigned)ceil_div(n_ids, 256), 256, 0, st>>>(ids, n_ids, n_rows, kbuf[cur], vbuf[cur], oob_flag);
-  int rc = check_launch("plan_init_kernel");
-  if (rc) return rc;
+  int rc;
+  {
+    ProfScope prof("plan_init_kernel", st);
+    plan_init_kernel<<<(unsigned)ceil_div(n_ids, 256), 256, 0, st>>>(ids, n_ids, n_rows, kbuf[cur], vbuf[cur], oob_flag);
+    if ((rc = check_launch("plan_init_kernel"))) return rc;
+  }
   for (int p = 0; p < passes; ++p) {
     const int shift = 8 * p;
-    radix_hist_kernel<<<nblk, 64, 0, st>>>(kbuf[cur], n_ids, shift, hist, nblk);
-    if ((rc = check_launch("radix_hist_kernel"))) return rc;
-    radix_scan_kernel<<<256, 64, 0, st>>>(hist, nblk, totals);
-    if ((rc = check_launch("radix_scan_kernel"))) return rc;
-    radix_scatter_kernel<<<nblk, 64, 0, st>>>(kbuf[cur], vbuf[cur], n_ids, shift, hist, nblk, totals, kbuf[cur ^ 1], vbuf[cur ^ 1]);
-    if ((rc = check_launch("radix_scatter_kernel"))) return rc;
+    {
+      ProfScope prof("radix_hist_kernel", st);
+      radix_hist_kernel<<<nblk, 64, 0, st>>>(kbuf[cur], n_ids, shift, hist, nblk);
+      if ((rc = check_launch("radix_hist_kernel"))) return rc;
+    }
+    {
+      ProfScope prof("radix_scan_kernel", st);
+      radix_scan_kernel<<<256, 64, 0, st>>>(hist, nblk, totals);
+      if ((rc = check_launch("radix_scan_kernel"))) return rc;
+    }
+    {
+      ProfScope prof("radix_scatter_kernel", st);
+      radix_scatter_kernel<<<nblk, 64, 0, st>>>(kbuf[cur], vbuf[cur], n_ids, shift, hist, nblk, totals, kbuf[cur ^ 1], vbuf[cur ^ 1]);
+      if ((rc = check_launch("radix_scatter_kernel"))) return rc;
+    }
     cur ^= 1;
   }
-  seg_count_kernel<<<nseg, 256, 0, st>>>(sorted_ids, n_ids, blk_heads);
-  if ((rc = check_launch("seg_count_kernel"))) return rc;
-  seg_scan_kernel<<<1, 256, 0, st>>>(blk_heads, nseg, n_ids, n_unique, seg_begin);
-  if ((rc = check_launch("seg_scan_kernel"))) return rc;
+  {
+    ProfScope prof("seg_count_kernel", st);
+    seg_count_kernel<<<nseg, 256, 0, st>>>(sorted_ids, n_ids, blk_heads);
+    if ((rc = check_launch("seg_count_kernel"))) return rc;
+  }
+  {
+    ProfScope prof("seg_scan_kernel", st);
+    seg_scan_kernel<<<1, 256, 0, st>>>(blk_heads, nseg, n_ids, n_unique, seg_begin);
+    if ((rc = check_launch("seg_scan_kernel"))) return rc;
+  }
+  ProfScope prof("seg_write_kernel", st);
   seg_write_kernel<<<nseg, 256, 0, st>>>(sorted_ids, n_ids, blk_heads, seg_begin);
   return check_launch("seg_write_kernel");
 }
@@ -440,7 +460,8 @@ extern "C" int tt_rowgrad_plan_jobs(const tt_plan_job* jobs, int32_t n_jobs, int
   for (int j = 0; j < n_jobs; ++j) {
     const tt_plan_job& b = jobs[j];
     if (!b.ids || !b.sorted_ids || !b.perm || !b.seg_begin || !b.n_unique) return fail_arg("tt_rowgrad_plan_jobs: null pointer");
-    if (b.n_ids <= 0 || b.n_ids > PS_MAX || b.n_rows <= 0 || b.n_rows > ((int64_t)1 << 31)) {
+    if (b.n_ids <= 0 || b.n_rows <= 0 || b.n_rows > ((int64_t)1 << 31)) return fail_arg("tt_rowgrad_plan_jobs: sizes");
+    if (b.n_ids > PS_MAX) {
       set_error("tt_rowgrad_plan_jobs: lists of 1..%d ids (longer ones: tt_rowgrad_plan)", PS_MAX);
       return TT_E_UNSUPPORTED;
     }
@@ -457,6 +478,7 @@ extern "C" int tt_rowgrad_plan_jobs(const tt_plan_job* jobs, int32_t n_jobs, int
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_small_jobs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { set_error("plan_small_jobs_kernel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
   }
+  ProfScope prof("plan_small_jobs_kernel", S(stream));
   plan_small_jobs_kernel<<<(unsigned)n_jobs, PS_THREADS, lds, S(stream)>>>(q, oob_flag);
   return check_launch("plan_small_jobs_kernel");
 }
