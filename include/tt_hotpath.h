@@ -295,6 +295,33 @@ int tt_inbatch_ce_bias_bwd(const float* U, int64_t ldu, const float* I, int64_t 
                            const float* coef, float* dU /* may be NULL */, int64_t lddu, float* dI, int64_t lddi, void* ws,
                            int64_t ws_bytes, tt_stream_t stream);
 
+/* The same calls with accidental hits removed from the in-batch softmax of ref:src/two_tower_base_retrieval.py:287-312
+ * (which counts every other row of the batch as a negative, ref:src/two_tower_base_retrieval.py:296-312, also a row that
+ * holds the user's own positive item).  With key = item_key [N] (32-bit item ids; equal keys <=> same item is the caller's
+ * contract) and pos(i) = i + diag_offset:
+ *   hit[i,j] = key[j] == key[pos(i)] and j != pos(i)          (the positive's own column is never masked)
+ *   row_ce[i] = logsumexp_{j : not hit[i,j]} S'[i,j] - S'[i,pos(i)],  S' as for the _bias_ calls (item_bias may be NULL)
+ *   G[i,j]  = coef[i] * (softmax over the unmasked columns - [j == pos(i)]),  G[i,j] = 0 where hit[i,j];  dU = G I,  dI = G^T U;
+ *   no gradient flows to the keys or to b.
+ * The mask is one compare and select where the logit is formed (S' is never written); kept logits hold the masked value,
+ * so tt_inbatch_ce_bwd_kept is the matching item-side backward, unchanged.  Any D the plain calls take.
+ * item_key == NULL: exactly what the _bias_ call does (ref:src/two_tower_base_retrieval.py:287-312, :289-295).
+ * `ws`: tt_inbatch_ce_masked_workspace_bytes(M, N, D).  The forward's optional outputs select the form as they do for
+ * tt_inbatch_ce_bias_fwd, with the same refusals (ref:src/two_tower_base_retrieval.py:287-312). */
+int64_t tt_inbatch_ce_masked_workspace_bytes(int64_t M, int64_t N, int64_t D);
+int tt_inbatch_ce_masked_fwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                             int64_t diag_offset, const float* item_bias /* [N], may be NULL */,
+                             const int32_t* item_key /* [N], may be NULL */, float* row_lse, float* row_ce,
+                             float* du_unit /* may be NULL */, int64_t ld_du, float* logits /* may be NULL */,
+                             int64_t logits_bytes, const float* labels /* may be NULL */, int64_t T,
+                             const float* uvw /* NULL: no loss tail */, float* w_out, float* coef_out, float* loss_out, void* ws,
+                             int64_t ws_bytes, tt_stream_t stream);
+int tt_inbatch_ce_masked_bwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                             int64_t diag_offset, const float* item_bias /* [N], may be NULL */,
+                             const int32_t* item_key /* [N], may be NULL */, const float* row_lse, const float* coef,
+                             float* dU /* may be NULL */, int64_t lddu, float* dI, int64_t lddi, void* ws, int64_t ws_bytes,
+                             tt_stream_t stream);
+
 /* Combined debias loss head (ref:src/two_tower_with_debiasing.py:77-129 on top of
  * ref:src/two_tower_base_retrieval.py:322-345), fused -- SURVEY 8f item 2:
  *   n = labels.uvw;  p = pos_table[position];  e = <user_emb, lin_w[:DI]> + p*lin_w[DI] + lin_b

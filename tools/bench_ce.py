@@ -1,5 +1,7 @@
 """Time the in-batch-softmax CE kernels alone (MI355X).  Usage: python tools/bench_ce.py [M N]
-The `*_bias` rows are the same forms with a per-item logit term (log-Q correction: tt_inbatch_ce_bias_fwd / _bwd)."""
+The `*_bias` rows are the same forms with a per-item logit term (log-Q correction: tt_inbatch_ce_bias_fwd / _bwd).
+--hits M N D: the cost of the accidental-hit mask instead -- the fused-loss forward and the item-side backward with the
+same term, item_key = NULL against Zipf-drawn keys (tt_inbatch_ce_masked_fwd / _bwd), in alternating rounds."""
 import os
 import sys
 
@@ -12,6 +14,59 @@ from two_tower_models_amd import ops
 
 lib = N.load()
 dev = torch.device("cuda:0")
+
+
+def hits_ab(M, Nn, D, rounds=7, reps=20):
+    """masked / unmasked time of the fused-loss forward and of the item-side backward: A B A B ..., one median per round."""
+    U, I = torch.randn(M, D, device=dev) * 0.3, torch.randn(Nn, D, device=dev) * 0.3
+    bias = torch.log(torch.randint(1, 10 ** 6, (Nn,), device=dev).float()) + 2.67
+    key = torch.floor(torch.pow(torch.tensor(float(Nn), device=dev), torch.rand(Nn, device=dev))).to(torch.int32)  # Zipf(1) ids
+    uvw = torch.ones(1, device=dev)
+    lse, ce, w, coef = (torch.empty(M, device=dev) for _ in range(4))
+    loss = torch.empty((), device=dev)
+    du, dI = torch.empty(M, D, device=dev), torch.empty(Nn, D, device=dev)
+    wsn = lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D)
+    ws = torch.empty(wsn, dtype=torch.uint8, device=dev)
+    head = (U.data_ptr(), D, I.data_ptr(), D, M, Nn, D, 0, bias.data_ptr())
+
+    def fwd(k):
+        N.check(lib.tt_inbatch_ce_masked_fwd(*head, k, lse.data_ptr(), ce.data_ptr(), du.data_ptr(), D, None, 0, None, 1, uvw.data_ptr(),
+                                             w.data_ptr(), coef.data_ptr(), loss.data_ptr(), ws.data_ptr(), wsn, N.stream()), "fwd")
+
+    def bwd(k):
+        N.check(lib.tt_inbatch_ce_masked_bwd(*head, k, lse.data_ptr(), coef.data_ptr(), None, D, dI.data_ptr(), D, ws.data_ptr(), wsn,
+                                             N.stream()), "bwd")
+
+    def timed(fn, k):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn(k)
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / reps
+
+    hit_rows = float((torch.bincount(key.long())[key.long()] > 1).float().mean())
+    for name, fn in (("fused-loss forward", fwd), ("item-side backward", bwd)):
+        fwd(key.data_ptr())  # (the backward reads this forward's lse and coef)
+        for k in (None, key.data_ptr()):
+            for _ in range(3):
+                fn(k)
+        torch.cuda.synchronize()
+        plain, masked = [], []
+        for _ in range(rounds):
+            plain.append(timed(fn, None))
+            masked.append(timed(fn, key.data_ptr()))
+        ratios = sorted(m / p for m, p in zip(masked, plain))
+        print(f"HITS_AB M={M} N={Nn} D={D} {name}: unmasked {sorted(plain)[rounds // 2] * 1e3:.1f} us, masked "
+              f"{sorted(masked)[rounds // 2] * 1e3:.1f} us, ratio median {ratios[rounds // 2]:.3f} (min {ratios[0]:.3f}, max {ratios[-1]:.3f} "
+              f"over {rounds} alternating rounds of {reps}); {100 * hit_rows:.0f} % of the items share their key", flush=True)
+
+
+if "--hits" in sys.argv:
+    at = sys.argv.index("--hits")
+    hits_ab(*(int(v) for v in sys.argv[at + 1:at + 4]))
+    sys.exit(0)
 shapes = [(8192, 8192), (8192, 65536)] if len(sys.argv) < 3 else [(int(sys.argv[1]), int(sys.argv[2]))]
 D = 128
 for M, Nn in shapes:

@@ -153,6 +153,11 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "tt_inbatch_ce_bias_bwd": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
                                       _i64, _vp]),
+    "tt_inbatch_ce_masked_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "tt_inbatch_ce_masked_fwd": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                        _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "tt_inbatch_ce_masked_bwd": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                        _vp, _i64, _vp]),
     "tt_ce16_supported": (_int, [_i64, _i64, _i64]),
     "tt_ce16_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "tt_ce16_fwd_du_keep": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),

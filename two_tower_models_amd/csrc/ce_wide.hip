@@ -18,10 +18,13 @@ constexpr float WIDE_NEG = -3.0e38f;
 // MODE 0: statistics only.  MODE 1: statistics, then S <- exp(S - lse).
 // bias (may be null): per-item additive term b[j], S'[i, j] = S[i, j] + b[j] (log-Q correction; the same one rounded
 // sum in the forward and the backward).
+// key (may be null): per-item 32-bit key; a column j != the positive's with key[j] == key[positive] is an accidental hit and
+// becomes WIDE_NEG in the materialised row (exp -> 0 in the sums, the probabilities and the gradient row).
 template <int MODE>
 __global__ __launch_bounds__(256) void wide_rows_fwd_kernel(float* __restrict__ S, int64_t N, int64_t lds, int64_t row0,
                                                             int64_t diag_offset, float* __restrict__ row_lse,
-                                                            float* __restrict__ row_ce, const float* __restrict__ bias) {
+                                                            float* __restrict__ row_ce, const float* __restrict__ bias,
+                                                            const int* __restrict__ key) {
   __shared__ float red[4];
   const int64_t r = blockIdx.x;  // row inside the chunk
   float* s = S + r * lds;
@@ -29,6 +32,12 @@ __global__ __launch_bounds__(256) void wide_rows_fwd_kernel(float* __restrict__ 
   float mx = WIDE_NEG;
   if (bias) {  // the corrected logits replace the plain ones in place: everything below reads S'
     for (int64_t j = threadIdx.x; j < N; j += 256) s[j] = s[j] + bias[j];
+  }
+  if (key) {
+    const int64_t d = row0 + r + diag_offset;
+    const int pk = key[d];
+    for (int64_t j = threadIdx.x; j < N; j += 256)
+      if (key[j] == pk && j != d) s[j] = WIDE_NEG;
   }
   for (int64_t j = threadIdx.x; j < N; j += 256) mx = fmaxf(mx, s[j]);
   mx = wave_max(mx);
@@ -56,11 +65,20 @@ __global__ __launch_bounds__(256) void wide_rows_fwd_kernel(float* __restrict__ 
 
 __global__ __launch_bounds__(256) void wide_rows_bwd_kernel(float* __restrict__ S, int64_t N, int64_t lds, int64_t row0,
                                                             int64_t diag_offset, const float* __restrict__ row_lse,
-                                                            const float* __restrict__ coef, const float* __restrict__ bias) {
+                                                            const float* __restrict__ coef, const float* __restrict__ bias,
+                                                            const int* __restrict__ key) {
   const int64_t r = blockIdx.x, g = row0 + r;
   float* s = S + r * lds;
   const float lse = row_lse[g], c = coef[g];
   const int64_t d = g + diag_offset;
+  if (key) {  // the same rounded logit as below, a hit's gradient entry is 0
+    const int pk = key[d];
+    for (int64_t j = threadIdx.x; j < N; j += 256) {
+      const float v = bias ? s[j] + bias[j] : s[j];
+      s[j] = (key[j] == pk && j != d) ? 0.f : (expf(v - lse) - (j == d ? 1.f : 0.f)) * c;
+    }
+    return;
+  }
   if (bias) {
     for (int64_t j = threadIdx.x; j < N; j += 256) s[j] = (expf((s[j] + bias[j]) - lse) - (j == d ? 1.f : 0.f)) * c;
     return;
@@ -102,7 +120,7 @@ int64_t ce_wide_workspace_bytes(int64_t M, int64_t N, int64_t D) {
 // mode 0: forward (lse, ce); 1: forward + du_unit; 2: backward (dU optional, dI)
 int ce_wide_run(int mode, const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
                 int64_t diag_offset, float* row_lse, float* row_ce, const float* coef, float* dU, int64_t lddu, float* dI,
-                int64_t lddi, void* ws, int64_t ws_bytes, hipStream_t st, const float* item_bias) {
+                int64_t lddi, void* ws, int64_t ws_bytes, hipStream_t st, const float* item_bias, const int* item_key) {
   if (ws_bytes < ce_wide_workspace_bytes(M, N, D)) { set_error("tt_inbatch_ce (D > 128): workspace"); return TT_E_WORKSPACE; }
   const int64_t mc = wide_chunk_rows(M, N);
   float* S = reinterpret_cast<float*>(ws);
@@ -116,10 +134,10 @@ int ce_wide_run(int mode, const float* U, int64_t ldu, const float* I, int64_t l
     if ((rc = tt_gemm_f32(TT_GEMM_NT, rows, N, D, Uc, ldu, I, ldi, S, N, nullptr, TT_EPI_NONE, nullptr, 0, 0, gws, gws_bytes, ts)))
       return rc;
     if (mode == 0) {
-      wide_rows_fwd_kernel<0><<<(unsigned)rows, 256, 0, st>>>(S, N, N, r0, diag_offset, row_lse, row_ce, item_bias);
+      wide_rows_fwd_kernel<0><<<(unsigned)rows, 256, 0, st>>>(S, N, N, r0, diag_offset, row_lse, row_ce, item_bias, item_key);
       if ((rc = check_launch("wide_rows_fwd_kernel"))) return rc;
     } else if (mode == 1) {
-      wide_rows_fwd_kernel<1><<<(unsigned)rows, 256, 0, st>>>(S, N, N, r0, diag_offset, row_lse, row_ce, item_bias);
+      wide_rows_fwd_kernel<1><<<(unsigned)rows, 256, 0, st>>>(S, N, N, r0, diag_offset, row_lse, row_ce, item_bias, item_key);
       if ((rc = check_launch("wide_rows_fwd_kernel"))) return rc;
       if ((rc = tt_gemm_f32(TT_GEMM_NN, rows, D, N, S, N, I, ldi, dU + r0 * lddu, lddu, nullptr, TT_EPI_NONE, nullptr, 0, 0, gws,
                             gws_bytes, ts)))
@@ -127,7 +145,7 @@ int ce_wide_run(int mode, const float* U, int64_t ldu, const float* I, int64_t l
       wide_sub_diag_kernel<<<(unsigned)ceil_div(rows * D, 256), 256, 0, st>>>(dU, lddu, I, ldi, rows, D, r0, diag_offset);
       if ((rc = check_launch("wide_sub_diag_kernel"))) return rc;
     } else {
-      wide_rows_bwd_kernel<<<(unsigned)rows, 256, 0, st>>>(S, N, N, r0, diag_offset, row_lse, coef, item_bias);
+      wide_rows_bwd_kernel<<<(unsigned)rows, 256, 0, st>>>(S, N, N, r0, diag_offset, row_lse, coef, item_bias, item_key);
       if ((rc = check_launch("wide_rows_bwd_kernel"))) return rc;
       if (dU && (rc = tt_gemm_f32(TT_GEMM_NN, rows, D, N, S, N, I, ldi, dU + r0 * lddu, lddu, nullptr, TT_EPI_NONE, nullptr, 0, 0,
                                   gws, gws_bytes, ts)))

@@ -60,6 +60,8 @@ struct CeArgs {
   unsigned* counter;  // fused loss epilogue: arrival counter of the finish kernel's blocks (zeroed by the product kernel)
   // BIAS kernels: per-ITEM additive logit term, pre-scaled to the log2 domain (b * log2 e), [number of items]
   const float* bias2;
+  // MASK kernels: per-ITEM 32-bit key, [number of items]; equal keys = same item (accidental hits are masked)
+  const int* key;
 };
 
 // ------------------------------------------------------------------ per-item logit term (template flag BIAS)
@@ -94,30 +96,30 @@ __device__ __forceinline__ int lane_id_here() {
 // with the tile -- by LDS-DMA next to the tile's own (GLDS), else fetched by threads 0..63 at `issue` and written at
 // `land`, the way ce_bwd_kernel<.., STREAM_STATS = true> stages lse / coef -- and are read back as float4 groups right
 // where they are consumed (never 16 values held across a sub-tile).
-template <bool BIAS, bool GLDS>
+template <bool BIAS, bool GLDS, typename T = float>
 struct BiasStage {
-  float v;
-  __device__ __forceinline__ void issue(const float* __restrict__ b2, int64_t row0, int64_t nrows, float* dst, int wave, int lane) {
+  T v;
+  __device__ __forceinline__ void issue(const T* __restrict__ b2, int64_t row0, int64_t nrows, float* dst, int wave, int lane) {
     if constexpr (BIAS && GLDS) {
       // LDS-DMA like the tile itself (one dword per lane of wave 0, 256 B lane-linear; terms past the end are outside
       // the descriptor's range and land as zeros): no staging register, no ds_write, completes under the tile's vmcnt(0)
       if (wave == 0) {
         const int l = lane_id_here();
         const int64_t left = nrows - row0;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b2 + row0), 0,
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(b2 + row0), 0,
                                                                             (left < BJ ? (int)left : BJ) * 4, 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 4, l * 4, 0, 0, 0);
       }
     } else if constexpr (BIAS) {
       if (threadIdx.x < BJ) {
         const int64_t b = row0 + threadIdx.x;
-        v = (b < nrows) ? b2[b] : 0.f;
+        v = (b < nrows) ? b2[b] : T(0);
       }
     }
   }
   __device__ __forceinline__ void land(float* dst) {
     if constexpr (BIAS && !GLDS) {
-      if (threadIdx.x < BJ) dst[threadIdx.x] = v;
+      if (threadIdx.x < BJ) reinterpret_cast<T*>(dst)[threadIdx.x] = v;
     }
   }
 };
@@ -128,13 +130,71 @@ __device__ __forceinline__ float4 bias_group(const float* sb, int q) {
   else return make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+
+// ------------------------------------------------------------------ accidental hits (template flag MASK)
+// hit[i, j] = key[j] == key[i + diag_offset] and j != i + diag_offset: another column that holds user i's own positive item
+// is no negative (TensorFlow Recommenders' remove_accidental_hits; the in-batch softmax of
+// ref:src/two_tower_base_retrieval.py:287-312 counts it as one).  The mask is applied where the logit is formed, in the
+// select that already turns a column past the end into NEG_BIG: fast_exp2 then yields 0 in the sums and in the gradient
+// tile.  MASK instantiations are BIAS = true ones (a zero term rounds like the plain multiply), so each kernel has three
+// forms, not four.  The keys travel as the terms do (KeyStage = BiasStage over int): a streamed tile's 64 keys ride behind
+// its terms (items streamed) or behind lse / coef (dI: the streamed users' POSITIVE keys, key[b + diag_offset]).  The
+// stationary row's key -- the user's positive key, or for dI the item's own -- is parked in LDS once and re-read per tile
+// (stat_key), not held across the tile loop: the D = 128 kernels have no register for it (see lane_id_here).
+template <bool MASK, bool GLDS>
+using KeyStage = BiasStage<MASK, GLDS, int>;
+template <bool MASK>
+__device__ __forceinline__ int4 key_group(const float* sk, int q) {  // as bias_group
+  if constexpr (MASK) return *reinterpret_cast<const int4*>(sk + 8 * q);
+  else return make_int4(0, 0, 0, 0);
+}
+template <bool MASK>
+__device__ __forceinline__ void park_stat_key(int* skey, int k, int wave, int r, int h) {
+  if constexpr (MASK) { if (h == 0) skey[wave * 32 + r] = k; }
+}
+template <bool MASK>
+__device__ __forceinline__ int stat_key(const int* skey, int wave) {
+  if constexpr (MASK) return skey[wave * 32 + (lane_id_here() & 31)];
+  else return 0;
+}
+// Items streamed: the mask as a SECOND pass over a sub-tile's 16 values (v[e] <- `masked` where hit), run once the terms'
+// registers are free again -- keys and terms held together cost the D = 128 kernels spills their BIAS twins do not have.
+// sk = the sub-tile's keys (tile + key offset + jt*32 + 4h).  want4 = -1000 (no positive in the tile): any equal key is a hit.
+// INVARIANT the online softmax relies on: a sub-tile whose 16 values are ALL masked while the running maximum is still
+// NEG_BIG contributes exp2(NEG_BIG - NEG_BIG) = 1 per value to s (and, in ce_fwd_du_kernel, p = 1 times its item rows to
+// dacc) -- finite garbage relative to a maximum of NEG_BIG.  It is removed, not avoided: the first finite maximum m rescales
+// what was accumulated by exp2(NEG_BIG - m) = 0, and a split that never sees one is merged with the factor
+// exp2(NEG_BIG - M) = 0 (ce_fwd_finish_kernel, ce_fwd_du_finish_row).  Every real user row reaches a finite maximum because
+// its positive's column is never masked and lies inside the item block; rows past the end are never written.  (The same
+// mechanism has always covered columns past the end of the last tile.)  The all_same key pattern of the tests is this case
+// in every tile but one.
+template <bool MASK, typename V>
+__device__ __forceinline__ void mask_hits(V& v, const float* sk, const int* skey, int wave, int jt, int want4, float masked) {
+  if constexpr (MASK) {
+    const int pk = stat_key<MASK>(skey, wave);  // this user's positive key
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int4 k4 = key_group<MASK>(sk, q);
+      const int kv[4] = {k4.x, k4.y, k4.z, k4.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int e = 4 * q + c;
+        const int li = jt * 32 + (e & 3) + 8 * (e >> 2);
+        v[e] = (kv[c] == pk && li != want4) ? masked : v[e];  // the positive's own column is never masked
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ forward
 // Streams tile t+1 while tile t is on the MFMA pipe.  GLDS: DMA issued at the top of the
 // iteration, drained (vmcnt(0)) right before the barrier that ends it.
-template <int DP8, bool GLDS, bool BIAS = false>
+template <int DP8, bool GLDS, bool BIAS = false, bool MASK = false>
 __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_kernel(const CeArgs p) {
+  static_assert(BIAS || !MASK, "MASK instantiations carry the term");
   using TM = TileMap<DP8, GLDS>;
-  constexpr int TILE_FLOATS = BJ * TM::LD + (BIAS ? BJ : 0);
+  constexpr int TILE_FLOATS = BJ * TM::LD + (BIAS ? BJ : 0) + (MASK ? BJ : 0);
+  __shared__ int skey[MASK ? BI : 1];
   // two NAMED tile buffers, loop unrolled by two (see ce_bwd_kept_kernel)
   __shared__ __attribute__((aligned(16))) float buf0[TILE_FLOATS];
   __shared__ __attribute__((aligned(16))) float buf1[TILE_FLOATS];
@@ -151,15 +211,19 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_kern
   float m = NEG_BIG, s = 0.f, dg = 0.f;
   bool has_dg = false;
   const int64_t want = a + p.diag_offset;
+  if constexpr (MASK) park_stat_key<MASK>(skey, a < p.RX ? p.key[want] : 0, wave, r, h);
 
   Stager<DP8, GLDS> stg;
   BiasStage<BIAS, GLDS> bst;
+  KeyStage<MASK, GLDS> kst;
   auto issue = [&](int64_t t, float* dst) {
     stg.issue(p.Y, p.ldy, t * BJ, p.RY, p.D, p.y_vec, dst, wave, lane);
     bst.issue(p.bias2, t * BJ, p.RY, dst + BJ * TM::LD, wave, lane);
+    kst.issue(p.key, t * BJ, p.RY, dst + BJ * TM::LD + BJ, wave, lane);
   };
   auto land = [&](float* dst) {
     bst.land(dst + BJ * TM::LD);
+    kst.land(dst + BJ * TM::LD + BJ);
     stg.land(dst);
   };
   if (t0 < t1) { issue(t0, buf0); land(buf0); }
@@ -190,6 +254,12 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_kern
           v2[e] = (li < lim4) ? s2 : NEG_BIG;
           tmax = fmaxf(tmax, v2[e]);
         }
+      }
+      if constexpr (MASK) {
+        mask_hits<MASK>(v2, sb + BJ, skey, wave, jt, want4, NEG_BIG);
+        tmax = NEG_BIG;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) tmax = fmaxf(tmax, v2[e]);
       }
       const float mn = fmaxf(m, tmax);
       float add = 0.f;
@@ -237,11 +307,14 @@ __global__ void ce_fwd_finish_kernel(const float* __restrict__ part_m, const flo
 // STREAM_STATS = false: stationary = users (stats per lane), streamed = items   -> dU
 // STREAM_STATS = true : stationary = items, streamed = users (stats per b)      -> dI
 // BIAS: the per-item term is per STREAMED row for dU (staged behind the tile, BiasStage) and one register per lane for dI.
-template <int DP8, bool STREAM_STATS, bool GLDS, bool BIAS = false>
+template <int DP8, bool STREAM_STATS, bool GLDS, bool BIAS = false, bool MASK = false>
 __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kernel(const CeArgs p) {
+  static_assert(BIAS || !MASK, "MASK instantiations carry the term");
   using TM = TileMap<DP8, GLDS>;
   constexpr int TD = (DP8 + 3) / 4;  // 32-column tiles of the output
-  constexpr int TILE_FLOATS = BJ * TM::LD + (STREAM_STATS ? 2 * BJ : (BIAS ? BJ : 0));
+  constexpr int KEY_AT = BJ * TM::LD + (STREAM_STATS ? 2 * BJ : BJ);  // MASK: the streamed rows' keys, behind the stats / the terms
+  constexpr int TILE_FLOATS = BJ * TM::LD + (STREAM_STATS ? 2 * BJ : (BIAS ? BJ : 0)) + (MASK ? BJ : 0);
+  __shared__ int skey[MASK ? BI : 1];
   // two NAMED tile buffers (see ce_bwd_kept_kernel): LDS reads of one do not wait for the DMA into the other
   __shared__ __attribute__((aligned(16))) float buf0[TILE_FLOATS];
   __shared__ __attribute__((aligned(16))) float buf1[TILE_FLOATS];
@@ -253,8 +326,15 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
 
   float lse2_a = 0.f, coef_a = 0.f;
   if (!STREAM_STATS && a < p.RX) { lse2_a = p.lse[a]; coef_a = p.coef[a]; }
+  // MASK, dU: the user's lse and coef are parked beside its key and re-read with it (one address, three reads per group)
+  __shared__ float sstat[(MASK && !STREAM_STATS) ? 2 * BI : 1];
+  if constexpr (MASK && !STREAM_STATS) {
+    if (h == 0) { sstat[wave * 32 + r] = lse2_a; sstat[BI + wave * 32 + r] = coef_a; }
+  }
   float bias_a = 0.f;  // dI: this lane's item term
   if constexpr (BIAS && STREAM_STATS) { if (a < p.RX) bias_a = p.bias2[a]; }
+  // MASK: dU parks the user's positive key, dI the item's own
+  if constexpr (MASK) park_stat_key<MASK>(skey, a < p.RX ? p.key[STREAM_STATS ? a : a + p.diag_offset] : 0, wave, r, h);
 
   const int64_t ntiles_all = (p.RY + BJ - 1) / BJ;
   const int64_t t0 = (int64_t)blockIdx.y * p.tiles_per_split;
@@ -274,10 +354,13 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
 
   Stager<DP8, GLDS> stg;
   BiasStage<BIAS && !STREAM_STATS, GLDS> bst;
+  KeyStage<MASK, GLDS> kst;
   float st_lse = 0.f, st_coef = 0.f;  // threads 0..63 stage the streamed rows' stats
   auto issue = [&](int64_t t, float* dst) {
     stg.issue(p.Y, p.ldy, t * BJ, p.RY, p.D, p.y_vec, dst, wave, lane);
     bst.issue(p.bias2, t * BJ, p.RY, dst + BJ * TM::LD, wave, lane);
+    // dI: streamed user b's positive key is key[b + diag_offset] (b < RY = M, so inside the item block)
+    kst.issue(STREAM_STATS ? p.key + p.diag_offset : p.key, t * BJ, p.RY, dst + KEY_AT, wave, lane);
     if (STREAM_STATS && threadIdx.x < BJ) {
       // BIAS: the item term took a register of the per-thread row offset kept across the loop (threads 0..63 are wave 0)
       const int64_t b = t * BJ + ((BIAS && GLDS) ? lane_id_here() : (int)threadIdx.x);
@@ -293,6 +376,7 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
       dst[BJ * TM::LD + BJ + tid] = st_coef;
     }
     bst.land(dst + BJ * TM::LD);
+    kst.land(dst + KEY_AT);
     stg.land(dst);
   };
 
@@ -308,6 +392,7 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
     // VALU instructions are paid in MFMA issue time (they do not co-execute): the diagonal test is
     // kept out of the tiles that do not hold this wave's diagonal (scalar ballot -> uniform branch)
     const bool no_diag = STREAM_STATS && __builtin_amdgcn_ballot_w64(want4 != -1000) == 0ull;
+    const int ka = stat_key<MASK && STREAM_STATS>(skey, wave);  // MASK, dI: this lane's own item key
 #pragma unroll
     for (int jt = 0; jt < 2; ++jt) {
       const f32x16 acc = score_tile<DP8, GLDS>(ys, xr, jt, r, h);
@@ -318,16 +403,32 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
         for (int q = 0; q < 4; ++q) {
           const float4 b4 = bias_group<BIAS>(sb, q);
           const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+          float sv[4];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) sv[c] = logit2_bwd<BIAS>(acc[4 * q + c], bv[c]);  // same rounded s2 as the forward
+          float lse_u = lse2_a, coef_u = coef_a;
+          if constexpr (MASK) {  // a hit's logit becomes NEG_BIG (the terms' registers are free again): p = 0, gradient 0
+            const int4 k4 = key_group<MASK>(ys + KEY_AT + jt * 32 + 4 * h, q);
+            const int kv[4] = {k4.x, k4.y, k4.z, k4.w};
+            const int u = wave * 32 + (lane_id_here() & 31);
+            const int pk = skey[u];  // this user's positive key
+            lse_u = sstat[u]; coef_u = sstat[BI + u];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const int li = jt * 32 + c + 8 * q;
+              sv[c] = (kv[c] == pk && li != want4) ? NEG_BIG : sv[c];
+            }
+          }
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const int e = 4 * q + c;
             const int li = jt * 32 + (e & 3) + 8 * (e >> 2);
-            const float pr = fast_exp2(logit2_bwd<BIAS>(acc[e], bv[c]) - lse2_a);  // same rounded s2 as the forward
-            const float gval = coef_a * (pr - ((li == want4) ? 1.f : 0.f));
+            const float pr = fast_exp2(sv[c] - lse_u);
+            const float gval = coef_u * (pr - ((li == want4) ? 1.f : 0.f));
             gt[e] = (li < lim4) ? gval : 0.f;
           }
         }
-      } else if (no_diag) {  // no diagonal in this tile for any lane of the wave: 4 instead of 7 VALU ops per element
+      } else if (no_diag) {  // (dI: ka below is the lane's own item key)  no diagonal in this tile for any lane of the wave: 4 instead of 7 VALU ops per element
         const float* sl = ys + BJ * TM::LD + jt * 32 + 4 * h;
         const float* sc = sl + BJ;
 #pragma unroll
@@ -338,6 +439,13 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
           gt[4 * q + 1] = c4.y * fast_exp2(logit2_bwd<BIAS>(acc[4 * q + 1], bias_a) - l4.y);
           gt[4 * q + 2] = c4.z * fast_exp2(logit2_bwd<BIAS>(acc[4 * q + 2], bias_a) - l4.z);
           gt[4 * q + 3] = c4.w * fast_exp2(logit2_bwd<BIAS>(acc[4 * q + 3], bias_a) - l4.w);
+          if constexpr (MASK) {  // no pair of this tile is a positive: an equal key is a hit
+            const int4 k4 = key_group<MASK>(sl + 2 * BJ, q);
+            gt[4 * q + 0] = (k4.x == ka) ? 0.f : gt[4 * q + 0];
+            gt[4 * q + 1] = (k4.y == ka) ? 0.f : gt[4 * q + 1];
+            gt[4 * q + 2] = (k4.z == ka) ? 0.f : gt[4 * q + 2];
+            gt[4 * q + 3] = (k4.w == ka) ? 0.f : gt[4 * q + 3];
+          }
         }
       } else {
         const float* sl = ys + BJ * TM::LD + jt * 32 + 4 * h;
@@ -347,12 +455,15 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_bwd_kern
           const float4 l4 = *reinterpret_cast<const float4*>(sl + 8 * q);
           const float4 c4 = *reinterpret_cast<const float4*>(sc + 8 * q);
           const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, cv[4] = {c4.x, c4.y, c4.z, c4.w};
+          const int4 k4 = key_group<MASK>(sl + 2 * BJ, q);
+          const int kv[4] = {k4.x, k4.y, k4.z, k4.w};
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const int e = 4 * q + c;
             const int li = jt * 32 + (e & 3) + 8 * (e >> 2);
             const float pr = fast_exp2(logit2_bwd<BIAS>(acc[e], bias_a) - lv[c]);
             gt[e] = cv[c] * (pr - ((li == want4) ? 1.f : 0.f));  // coef 0 beyond RY
+            if constexpr (MASK) gt[e] = (kv[c] == ka && li != want4) ? 0.f : gt[e];
           }
         }
       }
@@ -575,11 +686,13 @@ __global__ __launch_bounds__(256, 2) void ce_bwd_kept_kernel(const CeArgs p) {
 // KEEP: the masked log2-domain logits are also written to p.keep (16 B per lane and 4-row group), so
 // the item-side backward (ce_bwd_kept_kernel) reads them back instead of recomputing the product.
 // BIAS: the per-item terms are read as float4 groups inside the logit loop (the kernel has no 16 registers to spare).
-template <int DP8, bool GLDS, bool KEEP = false, bool BIAS = false>
+template <int DP8, bool GLDS, bool KEEP = false, bool BIAS = false, bool MASK = false>
 __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_du_kernel(const CeArgs p) {
+  static_assert(BIAS || !MASK, "MASK instantiations carry the term");
   using TM = TileMap<DP8, GLDS>;
   constexpr int TD = (DP8 + 3) / 4;
-  constexpr int TILE_FLOATS = BJ * TM::LD + (BIAS ? BJ : 0);
+  constexpr int TILE_FLOATS = BJ * TM::LD + (BIAS ? BJ : 0) + (MASK ? BJ : 0);
+  __shared__ int skey[MASK ? BI : 1];
   // two NAMED tile buffers (see ce_bwd_kept_kernel): LDS reads of one no longer wait for the DMA into the other
   __shared__ __attribute__((aligned(16))) float buf0[TILE_FLOATS];
   __shared__ __attribute__((aligned(16))) float buf1[TILE_FLOATS];
@@ -608,15 +721,19 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_du_k
   float m = NEG_BIG, s = 0.f;
   const int64_t want = (a < p.RX) ? a + p.diag_offset : -1;  // rows past the end own no diagonal
   const int zlane = KEEP ? ((wave * 32 + r) * (int)p.ldk + 4 * h) * 4 : 0;  // byte offset of this lane's logits row
+  if constexpr (MASK) park_stat_key<MASK>(skey, want >= 0 ? p.key[want] : 0, wave, r, h);
 
   Stager<DP8, GLDS> stg;
   BiasStage<BIAS, GLDS> bst;
+  KeyStage<MASK, GLDS> kst;
   auto issue = [&](int64_t t, float* dst) {
     stg.issue(p.Y, p.ldy, t * BJ, p.RY, p.D, p.y_vec, dst, wave, lane);
     bst.issue(p.bias2, t * BJ, p.RY, dst + BJ * TM::LD, wave, lane);
+    kst.issue(p.key, t * BJ, p.RY, dst + BJ * TM::LD + BJ, wave, lane);
   };
   auto land = [&](float* dst) {
     bst.land(dst + BJ * TM::LD);
+    kst.land(dst + BJ * TM::LD + BJ);
     stg.land(dst);
   };
   if (t0 < t1) { issue(t0, buf0); land(buf0); }
@@ -668,6 +785,12 @@ __global__ __launch_bounds__(256, ((GLDS || DP8 < 16) ? 2 : 1)) void ce_fwd_du_k
             tmax = fmaxf(tmax, v2[e]);
           }
         }
+      }
+      if constexpr (MASK) {  // before the kept logits are stored: they hold NEG_BIG for a hit
+        mask_hits<MASK>(v2, sb + BJ, skey, wave, jt, want4, NEG_BIG);
+        tmax = NEG_BIG;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) tmax = fmaxf(tmax, v2[e]);
       }
       if constexpr (KEEP) {  // rows past RX / columns past RY of the padded buffer get 0-logit / NEG_BIG filler
         // buffer stores: tile base in a scalar descriptor, one loop-invariant 32-bit lane offset
@@ -1019,7 +1142,8 @@ __global__ __launch_bounds__(256) void scale_rows_g_kernel(const float* __restri
 int64_t ce_wide_workspace_bytes(int64_t M, int64_t N, int64_t D);
 int ce_wide_run(int mode, const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
                 int64_t diag_offset, float* row_lse, float* row_ce, const float* coef, float* dU, int64_t lddu, float* dI,
-                int64_t lddi, void* ws, int64_t ws_bytes, hipStream_t st, const float* item_bias = nullptr);
+                int64_t lddi, void* ws, int64_t ws_bytes, hipStream_t st, const float* item_bias = nullptr,
+                const int* item_key = nullptr);
 
 struct CePlan {
   int dp8, splits;
@@ -1043,16 +1167,16 @@ static bool plan_ce(int64_t RX, int64_t RY, int64_t D, CePlan& pl) {
 }
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <int DP8, bool GLDS, bool BIAS>
+template <int DP8, bool GLDS, int BM>
 static int launch_fwd(const CeArgs& a, dim3 grid, hipStream_t st) {
   ProfScope prof("ce_fwd_kernel", st);
-  ce_fwd_kernel<DP8, GLDS, BIAS><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
+  ce_fwd_kernel<DP8, GLDS, (BM > 0), (BM > 1)><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
   return check_launch("ce_fwd_kernel");
 }
-template <int DP8, bool SS, bool GLDS, bool BIAS>
+template <int DP8, bool SS, bool GLDS, int BM>
 static int launch_bwd(const CeArgs& a, dim3 grid, hipStream_t st) {
   ProfScope prof("ce_bwd_kernel", st);
-  ce_bwd_kernel<DP8, SS, GLDS, BIAS><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
+  ce_bwd_kernel<DP8, SS, GLDS, (BM > 0), (BM > 1)><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
   return check_launch("ce_bwd_kernel");
 }
 // LDS-DMA staging needs an unpadded, fully valid row: D == padded D, 16-B aligned rows
@@ -1060,19 +1184,23 @@ static bool can_dma(const float* Y, int64_t ld, int64_t D, int dp8) {
   static const bool off = getenv("TT_CE_NO_DMA") != nullptr;
   return !off && D == dp8 * 8 && (ld % 4 == 0) && ld <= (1 << 22) && al16(Y);  // tile_dma: 32-bit byte offsets within a tile
 }
-// a.bias2 == nullptr: the BIAS = false instantiations, i.e. exactly the kernels the calls without a term launch
-template <bool BIAS>
+// BM (int BIAS below): 0 plain, 1 BIAS, 2 BIAS + MASK.
+// a.bias2 == nullptr: the BIAS = false instantiations, i.e. exactly the kernels the calls without a term launch;
+// a.key == nullptr: exactly the kernels the calls without keys launch (a.key comes with a.bias2, a zero term if need be)
+static inline int form_of(const CeArgs& a) { return a.key ? 2 : a.bias2 ? 1 : 0; }
+template <int BIAS>
 static int dispatch_fwd_b(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
   if (dma) return dp8 == 4 ? launch_fwd<4, true, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd<8, true, BIAS>(a, grid, st) : launch_fwd<16, true, BIAS>(a, grid, st);
   return dp8 == 4 ? launch_fwd<4, false, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd<8, false, BIAS>(a, grid, st) : launch_fwd<16, false, BIAS>(a, grid, st);
 }
 static int dispatch_fwd(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
-  return a.bias2 ? dispatch_fwd_b<true>(dp8, dma, a, grid, st) : dispatch_fwd_b<false>(dp8, dma, a, grid, st);
+  const int f = form_of(a);
+  return f == 2 ? dispatch_fwd_b<2>(dp8, dma, a, grid, st) : f ? dispatch_fwd_b<1>(dp8, dma, a, grid, st) : dispatch_fwd_b<0>(dp8, dma, a, grid, st);
 }
-template <int DP8, bool GLDS, bool KEEP, bool BIAS>
+template <int DP8, bool GLDS, bool KEEP, int BM>
 static int launch_fwd_du(const CeArgs& a, dim3 grid, hipStream_t st) {
   ProfScope prof("ce_fwd_kernel", st);
-  ce_fwd_du_kernel<DP8, GLDS, KEEP, BIAS><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
+  ce_fwd_du_kernel<DP8, GLDS, KEEP, (BM > 0), (BM > 1)><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
   return check_launch("ce_fwd_du_kernel");
 }
 template <int DP8>
@@ -1081,29 +1209,32 @@ static int launch_bwd_kept(const CeArgs& a, dim3 grid, hipStream_t st) {
   ce_bwd_kept_kernel<DP8><<<grid, 256, 0, st>>>(a);  // LDS is static: two named tile buffers
   return check_launch("ce_bwd_kept_kernel");
 }
-template <bool BIAS>
+template <int BIAS>
 static int dispatch_fwd_du_keep_b(int dp8, const CeArgs& a, dim3 grid, hipStream_t st) {  // LDS-DMA form only
   return dp8 == 4 ? launch_fwd_du<4, true, true, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, true, true, BIAS>(a, grid, st) : launch_fwd_du<16, true, true, BIAS>(a, grid, st);
 }
 static int dispatch_fwd_du_keep(int dp8, const CeArgs& a, dim3 grid, hipStream_t st) {
-  return a.bias2 ? dispatch_fwd_du_keep_b<true>(dp8, a, grid, st) : dispatch_fwd_du_keep_b<false>(dp8, a, grid, st);
+  const int f = form_of(a);
+  return f == 2 ? dispatch_fwd_du_keep_b<2>(dp8, a, grid, st) : f ? dispatch_fwd_du_keep_b<1>(dp8, a, grid, st) : dispatch_fwd_du_keep_b<0>(dp8, a, grid, st);
 }
-template <bool BIAS>
+template <int BIAS>
 static int dispatch_fwd_du_b(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
   if (dma) return dp8 == 4 ? launch_fwd_du<4, true, false, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, true, false, BIAS>(a, grid, st) : launch_fwd_du<16, true, false, BIAS>(a, grid, st);
   return dp8 == 4 ? launch_fwd_du<4, false, false, BIAS>(a, grid, st) : dp8 == 8 ? launch_fwd_du<8, false, false, BIAS>(a, grid, st) : launch_fwd_du<16, false, false, BIAS>(a, grid, st);
 }
 static int dispatch_fwd_du(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
-  return a.bias2 ? dispatch_fwd_du_b<true>(dp8, dma, a, grid, st) : dispatch_fwd_du_b<false>(dp8, dma, a, grid, st);
+  const int f = form_of(a);
+  return f == 2 ? dispatch_fwd_du_b<2>(dp8, dma, a, grid, st) : f ? dispatch_fwd_du_b<1>(dp8, dma, a, grid, st) : dispatch_fwd_du_b<0>(dp8, dma, a, grid, st);
 }
-template <bool SS, bool BIAS>
+template <bool SS, int BIAS>
 static int dispatch_bwd_b(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
   if (dma) return dp8 == 4 ? launch_bwd<4, SS, true, BIAS>(a, grid, st) : dp8 == 8 ? launch_bwd<8, SS, true, BIAS>(a, grid, st) : launch_bwd<16, SS, true, BIAS>(a, grid, st);
   return dp8 == 4 ? launch_bwd<4, SS, false, BIAS>(a, grid, st) : dp8 == 8 ? launch_bwd<8, SS, false, BIAS>(a, grid, st) : launch_bwd<16, SS, false, BIAS>(a, grid, st);
 }
 template <bool SS>
 static int dispatch_bwd(int dp8, bool dma, const CeArgs& a, dim3 grid, hipStream_t st) {
-  return a.bias2 ? dispatch_bwd_b<SS, true>(dp8, dma, a, grid, st) : dispatch_bwd_b<SS, false>(dp8, dma, a, grid, st);
+  const int f = form_of(a);
+  return f == 2 ? dispatch_bwd_b<SS, 2>(dp8, dma, a, grid, st) : f ? dispatch_bwd_b<SS, 1>(dp8, dma, a, grid, st) : dispatch_bwd_b<SS, 0>(dp8, dma, a, grid, st);
 }
 
 // b2[j] = b[j] * log2 e: the per-item term moved to the kernels' log2 domain, once per call
@@ -1134,12 +1265,12 @@ extern "C" int64_t tt_inbatch_ce_workspace_bytes(int64_t M, int64_t N, int64_t D
 // `bias`: the per-item term, natural-log units for D > 128 (ce_wide), pre-scaled to the log2 domain otherwise; may be null
 static int fwd_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
                     int64_t diag_offset, float* row_lse, float* row_ce, void* ws, int64_t ws_bytes, tt_stream_t stream,
-                    const float* bias) {
+                    const float* bias, const int* key = nullptr) {
   if (!U || !I || !row_lse || !row_ce || !ws) return fail_arg("tt_inbatch_ce_fwd: null pointer");
   if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D) return fail_arg("tt_inbatch_ce_fwd: sizes");
   if (diag_offset < 0 || diag_offset + M > N) return fail_arg("tt_inbatch_ce_fwd: diagonal outside the item block");
   if (D > 128)
-    return ce_wide_run(0, U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, nullptr, nullptr, 0, nullptr, 0, ws, ws_bytes, S(stream), bias);
+    return ce_wide_run(0, U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, nullptr, nullptr, 0, nullptr, 0, ws, ws_bytes, S(stream), bias, key);
   CePlan pl;
   if (!plan_ce(M, N, D, pl)) { set_error("tt_inbatch_ce: D=%lld > 128 not implemented", (long long)D); return TT_E_UNSUPPORTED; }
   if (ws_bytes < tt_inbatch_ce_workspace_bytes(M, N, D)) { set_error("tt_inbatch_ce_fwd: workspace"); return TT_E_WORKSPACE; }
@@ -1149,7 +1280,7 @@ static int fwd_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, in
   a.diag_offset = diag_offset; a.tiles_per_split = pl.tiles_per_split; a.splits = pl.splits;
   a.x_vec = (ldu % 4 == 0) && al16(U); a.y_vec = (ldi % 4 == 0) && al16(I);
   a.part_m = w; a.part_s = w + (int64_t)pl.splits * M; a.diag = w + 2 * (int64_t)pl.splits * M;
-  a.bias2 = bias;
+  a.bias2 = bias; a.key = key;
   dim3 grid((unsigned)ceil_div(M, BI), (unsigned)pl.splits);
   hipStream_t st = S(stream);
   int rc = dispatch_fwd(pl.dp8, can_dma(I, ldi, D, pl.dp8), a, grid, st);
@@ -1179,7 +1310,8 @@ struct CeLossTail {  // the weighted-mean loss head fused behind the forward (tt
 static int fwd_du_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N,
                        int64_t D, int64_t diag_offset, float* row_lse, float* row_ce, float* du_unit,
                        int64_t ld_du, float* logits, int64_t logits_bytes, void* ws, int64_t ws_bytes,
-                       tt_stream_t stream, const CeLossTail* tail = nullptr, const float* bias = nullptr);
+                       tt_stream_t stream, const CeLossTail* tail = nullptr, const float* bias = nullptr,
+                       const int* key = nullptr);
 
 extern "C" int tt_inbatch_ce_fwd_du(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N,
                                     int64_t D, int64_t diag_offset, float* row_lse, float* row_ce, float* du_unit,
@@ -1198,14 +1330,14 @@ extern "C" int tt_inbatch_ce_fwd_du_keep(const float* U, int64_t ldu, const floa
 static int fwd_du_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N,
                        int64_t D, int64_t diag_offset, float* row_lse, float* row_ce, float* du_unit,
                        int64_t ld_du, float* logits, int64_t logits_bytes, void* ws, int64_t ws_bytes,
-                       tt_stream_t stream, const CeLossTail* tail, const float* bias) {
+                       tt_stream_t stream, const CeLossTail* tail, const float* bias, const int* key) {
   if (!U || !I || !row_lse || !row_ce || !du_unit || !ws) return fail_arg("tt_inbatch_ce_fwd_du: null pointer");
   if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D || ld_du < D) return fail_arg("tt_inbatch_ce_fwd_du: sizes");
   if (diag_offset < 0 || diag_offset + M > N) return fail_arg("tt_inbatch_ce_fwd_du: diagonal outside the item block");
   if (D > 128) {
     if (logits) { set_error("tt_inbatch_ce_fwd_du_keep: needs D in {32, 64, 128} (use tt_inbatch_ce_fwd_du)"); return TT_E_UNSUPPORTED; }
     int rc = ce_wide_run(1, U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, nullptr, du_unit, ld_du, nullptr, 0, ws, ws_bytes,
-                         S(stream), bias);
+                         S(stream), bias, key);
     if (rc || !tail) return rc;
     weighted_mean_loss_kernel<<<1, 1024, 0, S(stream)>>>(tail->labels, M, tail->T, tail->uvw, row_ce, tail->w_out, tail->coef_out,
                                                          tail->loss_out);
@@ -1222,7 +1354,7 @@ static int fwd_du_impl(const float* U, int64_t ldu, const float* I, int64_t ldi,
   a.part_m = w; a.part_s = w + (int64_t)pl.splits * M; a.diag = w + 2 * (int64_t)pl.splits * M;
   a.out = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + round_up((2 * (int64_t)pl.splits * M + M) * 4, 256));
   if (tail) a.counter = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + tt_inbatch_ce_workspace_bytes(M, N, D) - 256);
-  a.bias2 = bias;
+  a.bias2 = bias; a.key = key;
   dim3 grid((unsigned)ceil_div(M, BI), (unsigned)pl.splits);
   hipStream_t st = S(stream);
   int rc;
@@ -1273,12 +1405,12 @@ extern "C" int tt_scale_rows_g(const float* x, int64_t ldx, const float* coef, c
 
 static int bwd_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
                     int64_t diag_offset, const float* row_lse, const float* coef, float* dU, int64_t lddu, float* dI,
-                    int64_t lddi, void* ws, int64_t ws_bytes, tt_stream_t stream, const float* bias) {
+                    int64_t lddi, void* ws, int64_t ws_bytes, tt_stream_t stream, const float* bias, const int* key = nullptr) {
   if (!U || !I || !row_lse || !coef || !dI || !ws) return fail_arg("tt_inbatch_ce_bwd: null pointer");
   if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D || (dU && lddu < D) || lddi < D) return fail_arg("tt_inbatch_ce_bwd: sizes");
   if (D > 128)
     return ce_wide_run(2, U, ldu, I, ldi, M, N, D, diag_offset, const_cast<float*>(row_lse), nullptr, coef, dU, lddu, dI, lddi, ws,
-                       ws_bytes, S(stream), bias);
+                       ws_bytes, S(stream), bias, key);
   CePlan pu, pi;
   if (!plan_ce(M, N, D, pu) || !plan_ce(N, M, D, pi)) { set_error("tt_inbatch_ce: D=%lld > 128 not implemented", (long long)D); return TT_E_UNSUPPORTED; }
   if (ws_bytes < tt_inbatch_ce_workspace_bytes(M, N, D)) { set_error("tt_inbatch_ce_bwd: workspace"); return TT_E_WORKSPACE; }
@@ -1292,7 +1424,7 @@ static int bwd_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, in
     a.X = U; a.Y = I; a.ldx = ldu; a.ldy = ldi; a.RX = M; a.RY = N; a.D = D; a.diag_offset = diag_offset;
     a.tiles_per_split = pu.tiles_per_split; a.splits = pu.splits;
     a.x_vec = (ldu % 4 == 0) && al16(U); a.y_vec = (ldi % 4 == 0) && al16(I);
-    a.lse = row_lse; a.coef = coef; a.out = pu.splits > 1 ? slab_u : dU; a.ldo = lddu; a.bias2 = bias;
+    a.lse = row_lse; a.coef = coef; a.out = pu.splits > 1 ? slab_u : dU; a.ldo = lddu; a.bias2 = bias; a.key = key;
     dim3 grid((unsigned)ceil_div(M, BI), (unsigned)pu.splits);
     rc = dispatch_bwd<false>(pu.dp8, can_dma(I, ldi, D, pu.dp8), a, grid, st);
     if (rc) return rc;
@@ -1305,7 +1437,7 @@ static int bwd_impl(const float* U, int64_t ldu, const float* I, int64_t ldi, in
     a.X = I; a.Y = U; a.ldx = ldi; a.ldy = ldu; a.RX = N; a.RY = M; a.D = D; a.diag_offset = diag_offset;
     a.tiles_per_split = pi.tiles_per_split; a.splits = pi.splits;
     a.x_vec = (ldi % 4 == 0) && al16(I); a.y_vec = (ldu % 4 == 0) && al16(U);
-    a.lse = row_lse; a.coef = coef; a.out = pi.splits > 1 ? slab_i : dI; a.ldo = lddi; a.bias2 = bias;
+    a.lse = row_lse; a.coef = coef; a.out = pi.splits > 1 ? slab_i : dI; a.ldo = lddi; a.bias2 = bias; a.key = key;
     dim3 grid((unsigned)ceil_div(N, BI), (unsigned)pi.splits);
     rc = dispatch_bwd<true>(pi.dp8, can_dma(U, ldu, D, pi.dp8), a, grid, st);
     if (rc) return rc;
@@ -1375,6 +1507,62 @@ extern "C" int tt_inbatch_ce_bias_bwd(const float* U, int64_t ldu, const float* 
   const float* bias = stage_bias(item_bias, M, N, D, ws, S(stream), &rc);
   if (rc) return rc;
   return bwd_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, coef, dU, lddu, dI, lddi, ws, ws_bytes, stream, bias);
+}
+
+// ------------------------------------------------------------------ the same calls with accidental hits masked
+extern "C" int64_t tt_inbatch_ce_masked_workspace_bytes(int64_t M, int64_t N, int64_t D) {
+  return tt_inbatch_ce_bias_workspace_bytes(M, N, D);  // the term's slot holds zeros when the caller gives no term
+}
+
+// the term the MASK kernels carry: the caller's (pre-scaled), or zeros (D <= 128; ce_wide takes a null term as it is)
+static const float* stage_masked_bias(const float* item_bias, int64_t M, int64_t N, int64_t D, void* ws, hipStream_t st, int* rc) {
+  if (item_bias || D > 128) return stage_bias(item_bias, M, N, D, ws, st, rc);
+  float* b2 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + tt_inbatch_ce_workspace_bytes(M, N, D));
+  const hipError_t e = hipMemsetAsync(b2, 0, (size_t)N * 4, st);
+  if (e != hipSuccess) { set_error("tt_inbatch_ce_masked: hipMemsetAsync: %s", hipGetErrorString(e)); *rc = (int)e; return nullptr; }
+  *rc = 0;
+  return b2;
+}
+
+extern "C" int tt_inbatch_ce_masked_fwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                                        int64_t diag_offset, const float* item_bias, const int32_t* item_key, float* row_lse,
+                                        float* row_ce, float* du_unit, int64_t ld_du, float* logits, int64_t logits_bytes,
+                                        const float* labels, int64_t T, const float* uvw, float* w_out, float* coef_out,
+                                        float* loss_out, void* ws, int64_t ws_bytes, tt_stream_t stream) {
+  if (!U || !I || !row_lse || !row_ce || !ws) return fail_arg("tt_inbatch_ce_masked_fwd: null pointer");
+  if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D || (du_unit && ld_du < D)) return fail_arg("tt_inbatch_ce_masked_fwd: sizes");
+  if (diag_offset < 0 || diag_offset + M > N) return fail_arg("tt_inbatch_ce_masked_fwd: diagonal outside the item block");
+  if (!du_unit && (logits || uvw)) return fail_arg("tt_inbatch_ce_masked_fwd: kept logits and the loss tail need du_unit");
+  if (uvw && (!w_out || !coef_out || !loss_out)) return fail_arg("tt_inbatch_ce_masked_fwd: null pointer");
+  if (uvw && labels && T <= 0) return fail_arg("tt_inbatch_ce_masked_fwd: sizes");
+  if (logits && uvw) { set_error("tt_inbatch_ce_masked_fwd: kept logits and the fused loss tail together"); return TT_E_UNSUPPORTED; }
+  if (!item_key)
+    return tt_inbatch_ce_bias_fwd(U, ldu, I, ldi, M, N, D, diag_offset, item_bias, row_lse, row_ce, du_unit, ld_du, logits, logits_bytes,
+                                  labels, T, uvw, w_out, coef_out, loss_out, ws, ws_bytes, stream);
+  if (ws_bytes < tt_inbatch_ce_masked_workspace_bytes(M, N, D)) { set_error("tt_inbatch_ce_masked_fwd: workspace"); return TT_E_WORKSPACE; }
+  int rc;
+  const float* bias = stage_masked_bias(item_bias, M, N, D, ws, S(stream), &rc);
+  if (rc) return rc;
+  if (!du_unit) return fwd_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, ws, ws_bytes, stream, bias, item_key);
+  const CeLossTail tail{labels, T, uvw, w_out, coef_out, loss_out};
+  return fwd_du_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, row_ce, du_unit, ld_du, logits, logits_bytes, ws, ws_bytes,
+                     stream, uvw ? &tail : nullptr, bias, item_key);
+}
+
+extern "C" int tt_inbatch_ce_masked_bwd(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t M, int64_t N, int64_t D,
+                                        int64_t diag_offset, const float* item_bias, const int32_t* item_key, const float* row_lse,
+                                        const float* coef, float* dU, int64_t lddu, float* dI, int64_t lddi, void* ws,
+                                        int64_t ws_bytes, tt_stream_t stream) {
+  if (!U || !I || !row_lse || !coef || !dI || !ws) return fail_arg("tt_inbatch_ce_masked_bwd: null pointer");
+  if (M <= 0 || N <= 0 || D <= 0 || ldu < D || ldi < D || (dU && lddu < D) || lddi < D) return fail_arg("tt_inbatch_ce_masked_bwd: sizes");
+  if (diag_offset < 0 || diag_offset + M > N) return fail_arg("tt_inbatch_ce_masked_bwd: diagonal outside the item block");
+  if (!item_key)
+    return tt_inbatch_ce_bias_bwd(U, ldu, I, ldi, M, N, D, diag_offset, item_bias, row_lse, coef, dU, lddu, dI, lddi, ws, ws_bytes, stream);
+  if (ws_bytes < tt_inbatch_ce_masked_workspace_bytes(M, N, D)) { set_error("tt_inbatch_ce_masked_bwd: workspace"); return TT_E_WORKSPACE; }
+  int rc;
+  const float* bias = stage_masked_bias(item_bias, M, N, D, ws, S(stream), &rc);
+  if (rc) return rc;
+  return bwd_impl(U, ldu, I, ldi, M, N, D, diag_offset, row_lse, coef, dU, lddu, dI, lddi, ws, ws_bytes, stream, bias, item_key);
 }
 
 extern "C" int tt_inbatch_ce_bwd_kept(const float* U, int64_t ldu, int64_t M, int64_t N, int64_t D, int64_t diag_offset,

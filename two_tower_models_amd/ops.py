@@ -8,6 +8,7 @@ allocator, the autograd tape and the stream.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import weakref
 import warnings
@@ -935,27 +936,67 @@ def _item_bias(item_bias: Optional[torch.Tensor], I: torch.Tensor, what: str) ->
     return item_bias.detach().contiguous()  # no gradient flows to the term
 
 
+def _item_key(item_key: Optional[torch.Tensor], I: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+    """The per-item key that marks accidental hits (equal keys = same item): int32 or int64 [N] on the items' device; the
+    kernels compare 32-bit values."""
+    if item_key is None:
+        return None
+    if not isinstance(item_key, torch.Tensor) or item_key.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what}: item_key must be an int32 or int64 tensor, got {getattr(item_key, 'dtype', type(item_key))}")
+    if item_key.device != I.device:
+        raise RuntimeError(f"{what}: item_key is on {item_key.device}, the item embeddings on {I.device}")
+    if item_key.dim() != 1 or item_key.shape[0] != I.shape[0]:
+        raise ValueError(f"{what}: item_key must have one value per item row, [{I.shape[0]}]; got {tuple(item_key.shape)}")
+    return item_key.detach().to(torch.int32).contiguous()  # no gradient flows to the keys
+
+
+def _takes_item_key(fn):
+    """Decorator of an autograd forward: one more trailing positional argument, `item_key`, behind `fn`'s own; it reaches
+    `fn` as `ctx.item_key_arg`.  `fn`'s own parameter list stays what introspection reports (functools.wraps, as
+    two_tower_base_retrieval.takes_history_lengths does for the models); the argument shows on the wrapper itself
+    (``inspect.signature(f, follow_wrapped=False)``)."""
+    own = fn.__code__.co_argcount  # ctx and fn's own inputs
+
+    @functools.wraps(fn)
+    def forward(ctx, *inputs, item_key: Optional[torch.Tensor] = None):
+        if len(inputs) > own:
+            raise TypeError(f"{fn.__qualname__}: at most {own} inputs (the last one item_key), got {len(inputs)}")
+        if len(inputs) == own:
+            inputs, item_key = inputs[:-1], inputs[-1]
+        ctx.item_key_arg = item_key
+        return fn(ctx, *inputs)
+    return forward
+
+
 class InBatchSoftmaxCE(torch.autograd.Function):
     """row_ce[i] = logsumexp_j S'[i, j] - S'[i, i + diag_offset],  S' = U I^T (+ item_bias[None, :])
     (torch.matmul + F.cross_entropy(reduction="none"), ref:...base_retrieval.py:287-312; the per-item term is the
-    log-Q correction ref:...base_retrieval.py:289-295 names as missing)."""
+    log-Q correction ref:...base_retrieval.py:289-295 names as missing).  With `item_key` the logsumexp leaves out every
+    column j != i + diag_offset whose key equals the positive's (accidental hits)."""
 
     @staticmethod
+    @_takes_item_key
     def forward(ctx, U, I, diag_offset: int = 0, keep_logits: Optional[bool] = None, item_bias: Optional[torch.Tensor] = None):
         """`keep_logits`: write the [M, N] logits out in the forward so the item-side backward does not
         recompute them (3 instead of 4 logit-sized products, for M*N*4 B of HBM each way).  Default:
         only for wide negative sets (N >= 4 M, i.e. several ranks' items per user) -- at N = M the
         step is bound by the Adam sweep's HBM traffic and the extra bytes cost more than the MFMAs.
         `item_bias`: float32 [N], added to every logit of its column (the positive included) inside the product
-        kernels; receives no gradient.  With it the fp32-MFMA kernels run (never the exploratory split-fp16 pair)."""
+        kernels; receives no gradient.  With it the fp32-MFMA kernels run (never the exploratory split-fp16 pair).
+        `item_key` (a sixth input, `apply(U, I, diag_offset, keep_logits, item_bias, item_key)`, see _takes_item_key):
+        int32 / int64 [N]; a column other than the positive's whose key equals the positive's is masked
+        inside the product kernels, forward and backward (tt_inbatch_ce_masked_fwd / _bwd).  Same kernels' routing
+        as with a term: never the split-fp16 pair."""
         dev = N.require_device(U, I)
         U, I = _rowmajor(U), _rowmajor(I)
         M, D = U.shape
         Nn = I.shape[0]
         lib = N.load()
         item_bias = _item_bias(item_bias, I, "InBatchSoftmaxCE")
-        if item_bias is not None:
-            return InBatchSoftmaxCE._forward_biased(ctx, lib, dev, U, I, M, Nn, D, diag_offset, keep_logits, item_bias)
+        item_key = _item_key(ctx.item_key_arg, I, "InBatchSoftmaxCE")
+        ctx.keyed = item_key is not None
+        if item_bias is not None or item_key is not None:
+            return InBatchSoftmaxCE._forward_biased(ctx, lib, dev, U, I, M, Nn, D, diag_offset, keep_logits, item_bias, item_key)
         ctx.biased = False
         lse = torch.empty(M, dtype=torch.float32, device=dev)
         ce = torch.empty(M, dtype=torch.float32, device=dev)
@@ -1006,9 +1047,10 @@ class InBatchSoftmaxCE(torch.autograd.Function):
         return ce
 
     @staticmethod
-    def _forward_biased(ctx, lib, dev, U, I, M, Nn, D, diag_offset, keep_logits, item_bias):
-        """The same three forms (plain / + du_unit / + kept logits) through tt_inbatch_ce_bias_fwd."""
-        ctx.biased = True
+    def _forward_biased(ctx, lib, dev, U, I, M, Nn, D, diag_offset, keep_logits, item_bias, item_key=None):
+        """The same three forms (plain / + du_unit / + kept logits) through tt_inbatch_ce_bias_fwd, or with keys through
+        tt_inbatch_ce_masked_fwd (the term may then be absent)."""
+        ctx.biased = item_bias is not None
         ctx.diag_offset = diag_offset
         ctx.kept = ctx.kept16 = None
         lse = torch.empty(M, dtype=torch.float32, device=dev)
@@ -1032,22 +1074,26 @@ class InBatchSoftmaxCE(torch.autograd.Function):
                 zn = lib.tt_inbatch_ce_logits_bytes(M, Nn)
                 ctx.kept = torch.empty(zn, dtype=torch.uint8, device=dev)
                 zp = ctx.kept.data_ptr()
-        N.check(lib.tt_inbatch_ce_bias_fwd(pu, ldu, pi, ldi, M, Nn, D, diag_offset, item_bias.data_ptr(), lse.data_ptr(), ce.data_ptr(),
-                                           N.ptr(du_unit), D, zp, zn, None, 0, None, None, None, None, wsp, wsn, N.stream()),
-                "tt_inbatch_ce_bias_fwd")
-        if du_unit is not None:
-            ctx.save_for_backward(U, I, lse, item_bias, du_unit)
+        if item_key is not None:
+            N.check(lib.tt_inbatch_ce_masked_fwd(pu, ldu, pi, ldi, M, Nn, D, diag_offset, N.ptr(item_bias), item_key.data_ptr(),
+                                                 lse.data_ptr(), ce.data_ptr(), N.ptr(du_unit), D, zp, zn, None, 0, None, None, None,
+                                                 None, wsp, wsn, N.stream()), "tt_inbatch_ce_masked_fwd")
         else:
-            ctx.save_for_backward(U, I, lse, item_bias)
+            N.check(lib.tt_inbatch_ce_bias_fwd(pu, ldu, pi, ldi, M, Nn, D, diag_offset, item_bias.data_ptr(), lse.data_ptr(), ce.data_ptr(),
+                                               N.ptr(du_unit), D, zp, zn, None, 0, None, None, None, None, wsp, wsn, N.stream()),
+                    "tt_inbatch_ce_bias_fwd")
+        ctx.save_for_backward(U, I, lse, *[t for t in (item_bias, item_key, du_unit) if t is not None])
         return ce
 
     @staticmethod
     def backward(ctx, d_ce):
         saved = ctx.saved_tensors
         U, I, lse = saved[:3]
-        item_bias = None
+        item_bias = item_key = None
         if ctx.biased:
             item_bias, saved = saved[3], saved[:3] + saved[4:]
+        if ctx.keyed:
+            item_key, saved = saved[3], saved[:3] + saved[4:]
         du_unit = saved[3] if len(saved) > 3 else None
         dev = U.device
         M, D = U.shape
@@ -1058,8 +1104,8 @@ class InBatchSoftmaxCE(torch.autograd.Function):
         if du_unit is not None:
             N.check(lib.tt_scale_rows(du_unit.data_ptr(), D, coef.data_ptr(), M, D, dU.data_ptr(), D, N.stream()), "tt_scale_rows")
         dI = torch.empty(Nn, D, dtype=torch.float32, device=dev)
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D) if item_bias is None
-                       else lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
+        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D) if (item_bias is None and item_key is None)
+                       else lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D))  # (= the _bias_ calls' size)
         pu, _, _, ldu = _f32_2d(U, "U")
         pi, _, _, ldi = _f32_2d(I, "I")
         before = None
@@ -1068,13 +1114,15 @@ class InBatchSoftmaxCE(torch.autograd.Function):
             before.record()
         try:
             return InBatchSoftmaxCE._item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn,
-                                               item_bias)
+                                               item_bias, item_key)
         finally:
             if before is not None:
                 _release_held_sweeps(before)
 
     @staticmethod
-    def _item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn, item_bias=None):
+    def _item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn, item_bias=None, item_key=None):
+        # every path returns SIX entries, one per input `apply` can be given (U, I, diag_offset, keep_logits, item_bias,
+        # item_key): autograd wants at least as many as it was given and ignores trailing None beyond them
         if ctx.kept16 is not None:  # the split-fp16 pair's backward
             w16p, w16n = _ws(dev, lib.tt_ce16_workspace_bytes(M, Nn, D), "ce16")
             if ctx.kept16 is True:  # (images formed again: other products may have used the workspace slot since the forward)
@@ -1084,22 +1132,27 @@ class InBatchSoftmaxCE(torch.autograd.Function):
                 N.check(lib.tt_ce16_bwd_kept(pu, D, M, Nn, D, ctx.diag_offset, lse.data_ptr(), coef.data_ptr(), ctx.kept16.data_ptr(),
                                              M * Nn * 4, dI.data_ptr(), D, w16p, w16n, N.stream()), "tt_ce16_bwd_kept")
             ctx.kept16 = None
-            return dU, dI, None, None, None
-        if ctx.kept is not None:  # item side from the logits the forward kept (they include the per-item term, if any)
+            return dU, dI, None, None, None, None
+        if ctx.kept is not None:  # item side from the logits the forward kept (they include the per-item term and the mask, if any)
             N.check(lib.tt_inbatch_ce_bwd_kept(pu, ldu, M, Nn, D, ctx.diag_offset, lse.data_ptr(), coef.data_ptr(),
                                                ctx.kept.data_ptr(), ctx.kept.numel(), dI.data_ptr(), D, wsp, wsn,
                                                N.stream()), "tt_inbatch_ce_bwd_kept")
             ctx.kept = None
-            return dU, dI, None, None, None
+            return dU, dI, None, None, None, None
+        if item_key is not None:
+            N.check(lib.tt_inbatch_ce_masked_bwd(pu, ldu, pi, ldi, M, Nn, D, ctx.diag_offset, N.ptr(item_bias), item_key.data_ptr(),
+                                                 lse.data_ptr(), coef.data_ptr(), None if du_unit is not None else dU.data_ptr(), D,
+                                                 dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_masked_bwd")
+            return dU, dI, None, None, None, None
         if item_bias is not None:
             N.check(lib.tt_inbatch_ce_bias_bwd(pu, ldu, pi, ldi, M, Nn, D, ctx.diag_offset, item_bias.data_ptr(), lse.data_ptr(),
                                                coef.data_ptr(), None if du_unit is not None else dU.data_ptr(), D,
                                                dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bias_bwd")
-            return dU, dI, None, None, None
+            return dU, dI, None, None, None, None
         N.check(lib.tt_inbatch_ce_bwd(pu, ldu, pi, ldi, M, Nn, D, ctx.diag_offset, lse.data_ptr(),
                                       coef.data_ptr(), None if du_unit is not None else dU.data_ptr(), D,
                                       dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bwd")
-        return dU, dI, None, None, None
+        return dU, dI, None, None, None, None
 
 
 def _labels_f32(labels: torch.Tensor, what: str) -> torch.Tensor:
@@ -1162,11 +1215,11 @@ def ce16_usable(U: torch.Tensor, I: torch.Tensor) -> bool:
 
 
 def fused_loss_supported(U: torch.Tensor, I: torch.Tensor, labels: Optional[torch.Tensor], uvw: torch.Tensor,
-                         item_bias: Optional[torch.Tensor] = None) -> bool:
+                         item_bias: Optional[torch.Tensor] = None, item_key: Optional[torch.Tensor] = None) -> bool:
     """InBatchSoftmaxWeightedLoss: a training forward (U needs a gradient) with in-batch negatives only (N < 4 M: the wide
     form keeps its logits and has its own forward), float32 everywhere, one label row per user row."""
-    if item_bias is None and ce16_usable(U, I):
-        return False  # the split-fp16 pair is a two-op path: InBatchSoftmaxCE + WeightedMeanLoss (never taken with a bias)
+    if item_bias is None and item_key is None and ce16_usable(U, I):
+        return False  # the split-fp16 pair is a two-op path: InBatchSoftmaxCE + WeightedMeanLoss (never taken with a bias or keys)
     return bool(U.is_cuda and U.requires_grad and torch.is_grad_enabled() and U.dim() == 2 and I.dim() == 2
                 and U.dtype == torch.float32 and I.dtype == torch.float32 and uvw.dtype == torch.float32
                 and I.shape[0] < 4 * U.shape[0]
@@ -1179,16 +1232,19 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
     the forward (tt_inbatch_ce_fwd_du_loss; ref:src/two_tower_base_retrieval.py:287-312,322,334-343), and the backward
     starts with ONE launch that forms dL/dce * g and dU (tt_scale_rows_g) instead of an elementwise multiply and a row
     scaling.  Same values as the two ops, bit for bit; two launches fewer on the step's critical path.
-    `item_bias` (float32 [N], optional): the per-item logit term of InBatchSoftmaxCE; no gradient."""
+    `item_bias` (float32 [N], optional): the per-item logit term of InBatchSoftmaxCE; no gradient.
+    `item_key` (int32 / int64 [N], optional sixth input, see _takes_item_key): accidental hits masked as in InBatchSoftmaxCE; no gradient."""
 
     @staticmethod
+    @_takes_item_key
     def forward(ctx, U, I, labels, uvw, item_bias: Optional[torch.Tensor] = None):
         dev = N.require_device(U, I, labels, uvw)
         U, I, uvw = _rowmajor(U), _rowmajor(I), uvw.contiguous()
         M, D = U.shape
         Nn = I.shape[0]
         item_bias = _item_bias(item_bias, I, "InBatchSoftmaxWeightedLoss")
-        ctx.biased = item_bias is not None
+        item_key = _item_key(ctx.item_key_arg, I, "InBatchSoftmaxWeightedLoss")
+        ctx.biased, ctx.keyed = item_bias is not None, item_key is not None
         T = 1
         if labels is not None:
             labels = _labels_f32(labels, "InBatchSoftmaxWeightedLoss")
@@ -1205,6 +1261,14 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
         du_unit = torch.empty(M, D, dtype=torch.float32, device=dev)
         pu, _, _, ldu = _f32_2d(U, "U")
         pi, _, _, ldi = _f32_2d(I, "I")
+        if item_key is not None:
+            wsp, wsn = _ws(dev, lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D))
+            N.check(lib.tt_inbatch_ce_masked_fwd(pu, ldu, pi, ldi, M, Nn, D, 0, N.ptr(item_bias), item_key.data_ptr(), lse.data_ptr(),
+                                                 ce.data_ptr(), du_unit.data_ptr(), D, None, 0, N.ptr(labels), T, uvw.data_ptr(),
+                                                 w.data_ptr(), coef.data_ptr(), loss.data_ptr(), wsp, wsn, N.stream()),
+                    "tt_inbatch_ce_masked_fwd")
+            ctx.save_for_backward(U, I, lse, du_unit, coef, *[t for t in (item_bias, item_key) if t is not None])
+            return loss
         if item_bias is not None:
             wsp, wsn = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
             N.check(lib.tt_inbatch_ce_bias_fwd(pu, ldu, pi, ldi, M, Nn, D, 0, item_bias.data_ptr(), lse.data_ptr(), ce.data_ptr(),
@@ -1223,6 +1287,7 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
     def backward(ctx, g):
         U, I, lse, du_unit, coef = ctx.saved_tensors[:5]
         item_bias = ctx.saved_tensors[5] if ctx.biased else None
+        item_key = ctx.saved_tensors[-1] if ctx.keyed else None
         dev = U.device
         M, D = U.shape
         Nn = I.shape[0]
@@ -1235,15 +1300,21 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
         dI = torch.empty(Nn, D, dtype=torch.float32, device=dev)
         pu, _, _, ldu = _f32_2d(U, "U")
         pi, _, _, ldi = _f32_2d(I, "I")
+        if item_key is not None:
+            wsp, wsn = _ws(dev, lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D))
+            N.check(lib.tt_inbatch_ce_masked_bwd(pu, ldu, pi, ldi, M, Nn, D, 0, N.ptr(item_bias), item_key.data_ptr(), lse.data_ptr(),
+                                                 coef_g.data_ptr(), None, D, dI.data_ptr(), D, wsp, wsn, N.stream()),
+                    "tt_inbatch_ce_masked_bwd")
+            return dU, dI, None, None, None, None
         if item_bias is not None:
             wsp, wsn = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
             N.check(lib.tt_inbatch_ce_bias_bwd(pu, ldu, pi, ldi, M, Nn, D, 0, item_bias.data_ptr(), lse.data_ptr(), coef_g.data_ptr(),
                                                None, D, dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bias_bwd")
-            return dU, dI, None, None, None
+            return dU, dI, None, None, None, None
         wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
         N.check(lib.tt_inbatch_ce_bwd(pu, ldu, pi, ldi, M, Nn, D, 0, lse.data_ptr(), coef_g.data_ptr(), None, D,
                                       dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bwd")
-        return dU, dI, None, None, None
+        return dU, dI, None, None, None, None
 
 
 class DebiasedWeightedLoss(torch.autograd.Function):

@@ -88,9 +88,13 @@ class DeviceBatches:
 class CandidateSampler:
     """What ``--logq`` / ``--num_random_negatives`` add to a batch, drawn on the device: the log sampling probability of
     the batch's own items (unigram table of the data set's item ids, built once) and, per step, Bn uniform item ids with
-    ``randn`` features from a seeded generator.  With both, log q is the mixture form (sampling.mixture_log_q)."""
+    ``randn`` features from a seeded generator.  With both, log q is the mixture form (sampling.mixture_log_q).
+    ``remove_accidental_hits``: every batch also asks ``train_forward`` to mask the candidates that hold a user's own
+    positive item (``--remove_accidental_hits``)."""
 
-    def __init__(self, dataset: DummyRecDataset, logq: bool, num_random_negatives: int, seed: int = 4321):
+    def __init__(self, dataset: DummyRecDataset, logq: bool, num_random_negatives: int, seed: int = 4321,
+                 remove_accidental_hits: bool = False):
+        self.remove_hits = bool(remove_accidental_hits)
         dev = dataset.item_ids.device
         self.num_items, self.feature_dim, self.n_neg = dataset.num_items, dataset.feature_dim, int(num_random_negatives)
         self.gen = torch.Generator(device=dev).manual_seed(seed)
@@ -101,6 +105,8 @@ class CandidateSampler:
     def __call__(self, item_ids: torch.Tensor) -> dict:
         """Keywords for ``train_forward`` for the batch whose items are ``item_ids``."""
         kw, B, dev = {}, item_ids.shape[0], item_ids.device
+        if self.remove_hits:
+            kw["remove_accidental_hits"] = True
         neg = None
         if self.n_neg > 0:
             neg = torch.randint(0, self.num_items, (self.n_neg,), device=dev, generator=self.gen)
@@ -193,6 +199,9 @@ def main(args):
         raise SystemExit("--num_random_negatives must be >= 0")
     if world > 1 and (logq or n_neg):
         raise SystemExit("--logq / --num_random_negatives are not implemented with --world_size > 1 (row-sharded tables)")
+    hits = bool(getattr(args, "remove_accidental_hits", False))
+    if world > 1 and hits:
+        raise SystemExit("--remove_accidental_hits is not implemented with --world_size > 1 (row-sharded tables)")
     min_len = getattr(args, "min_history_len", None)
     if min_len is not None and world > 1:
         raise SystemExit("--min_history_len is not implemented with --world_size > 1 (row-sharded tables)")
@@ -228,7 +237,7 @@ def main(args):
     # forward-announced sweep start assumes (optim.py)
     optimizer = DenseExactAdam(model.parameters(), lr=args.learning_rate, overlap_sweep="forward",
                                lazy=getattr(args, "lazy_adam", False))
-    candidates = CandidateSampler(dataset, logq, n_neg) if (logq or n_neg) else None
+    candidates = CandidateSampler(dataset, logq, n_neg, remove_accidental_hits=hits) if (logq or n_neg or hits) else None
     lengths = HistoryLengthSampler(args.user_history_seqlen, min_len, device) if min_len is not None else None
     stats = []
     for epoch in range(args.num_epochs):
@@ -310,6 +319,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--logq", action="store_true",
                    help="log-Q sampling-bias correction of the in-batch softmax: subtract log q_j (unigram table of the data "
                         "set's item ids; with --num_random_negatives the unigram / uniform mixture) from every logit column")
+    p.add_argument("--remove_accidental_hits", action="store_true",
+                   help="in-batch softmax: a candidate that holds the same item id as a user's positive (another row of the "
+                        "batch, or a --num_random_negatives draw) is not counted as a negative for that user; the usual "
+                        "companion of --logq")
     p.add_argument("--num_random_negatives", type=int, default=0,
                    help="mixed negative sampling: this many uniformly drawn items (random features) per step next to the "
                         "in-batch negatives")

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 from . import _native as N
 from . import ops
 from .baseline_mips_module import BaselineMIPSModule
-from .two_tower_base_retrieval import takes_history_lengths
+from .two_tower_base_retrieval import _REMOVE_HITS, takes_history_lengths, takes_remove_accidental_hits
 from .two_tower_with_debiasing import TwoTowerWithDebiasing
 
 _WEIGHT_MIN = 1.0e-6  # ref :282-284
@@ -132,6 +132,7 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
 
     # ------------------------------------------------------------------ training
     @takes_history_lengths
+    @takes_remove_accidental_hits
     def train_forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor,
                       item_id: torch.Tensor, item_features: torch.Tensor, position: torch.Tensor,
                       labels: torch.Tensor, item_log_q=None, negative_item_id=None, negative_item_features=None,
@@ -139,20 +140,25 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
         """MIPS term + light ranker term (ref :211-340).  No host synchronisation: GraphedTrainStep captures it.
         The log-Q / extra-negative keywords of TwoTowerBaseRetrieval.train_forward are refused: the ranker term scores
         the impressed item only and has no corrected form here.  ``user_history_lengths`` is refused as well
-        (`_history_lengths`)."""
+        (`_history_lengths`).  ``remove_accidental_hits``: as in TwoTowerBaseRetrieval.train_forward, on the MIPS term."""
         if any(t is not None for t in (item_log_q, negative_item_id, negative_item_features, negative_log_q)):
             raise NotImplementedError("TwoTowerPlusLightRanker.train_forward: item_log_q / negative_* are not implemented "
                                       "for the light-ranker model")
         self._check_unsharded("train_forward")
+        remove_accidental_hits = _REMOVE_HITS.get()
+        if remove_accidental_hits and self.item_id_embedding_arch.num_embeddings > 2 ** 31:
+            raise ValueError("train_forward: remove_accidental_hits compares item ids as 32-bit values; "
+                             f"item_id_hash_size = {self.item_id_embedding_arch.num_embeddings} > 2 ** 31")
         self._announce_lookups(user_id, user_history, item_id)
         u, R = self.compute_user_embedding(user_id, user_features, user_history)  # [B, DI], [B, NU, DI]
         v = self.compute_item_embeddings(item_id, item_features)  # [B, DI]
-        return self._mips_loss(u, v, position, labels) + self._ranker_loss(u, R, v, labels)
+        return self._mips_loss(u, v, position, labels, item_id if remove_accidental_hits else None) + self._ranker_loss(u, R, v, labels)
 
-    def _mips_loss(self, u, v, position, labels) -> torch.Tensor:
+    def _mips_loss(self, u, v, position, labels, item_key=None) -> torch.Tensor:
         """ref :256-296: in-batch softmax CE per row, weighted by the (debiased) net user value clamped at 1e-6 -- no
         division by the batch maximum here (module docstring)."""
-        row_ce = ops.InBatchSoftmaxCE.apply(u, v, 0)  # [B], the [B, B] logits never written
+        # [B], the [B, B] logits never written; item_key: accidental hits masked
+        row_ce = ops.InBatchSoftmaxCE.apply(u, v, 0) if item_key is None else ops.InBatchSoftmaxCE.apply(u, v, 0, None, None, item_key)
         net_user_value = torch.matmul(labels, self.user_value_weights)  # [B]
         net_user_value, additional_loss = self.debias_net_user_value(net_user_value, position, u)
         net_user_value = torch.clamp(net_user_value, min=_WEIGHT_MIN)
