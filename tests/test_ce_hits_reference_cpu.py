@@ -169,42 +169,59 @@ def test_header_loader_and_abi_version():
 
 
 def test_model_and_op_arguments_exist():
-    """The new arguments ride on wrappers, as user_history_lengths does: the wrapped functions keep the parameter lists
-    that tests/test_logq_cpu.py pins, the wrappers show the new keyword."""
+    """The new arguments are plain parameters of the methods and of the autograd forwards; only `user_history_lengths`
+    still rides on a wrapper (`takes_history_lengths`)."""
     import two_tower_models_amd as A
     from two_tower_models_amd import ops
-    own = lambda f: inspect.signature(f, follow_wrapped=False).parameters
+    own = lambda f: inspect.signature(f).parameters
     base = A.TwoTowerBaseRetrieval
-    assert own(base.train_forward.__wrapped__)["remove_accidental_hits"].default is False  # (inside takes_history_lengths)
+    assert own(base.train_forward)["remove_accidental_hits"].default is False
     assert own(base.compute_training_loss)["item_id"].default is None
     assert own(ops.InBatchSoftmaxCE.forward)["item_key"].default is None
     assert own(ops.InBatchSoftmaxWeightedLoss.forward)["item_key"].default is None
+    assert not hasattr(base.compute_training_loss, "__wrapped__") and not hasattr(ops.InBatchSoftmaxCE.forward, "__wrapped__")
+    assert not hasattr(base.train_forward.__wrapped__, "__wrapped__")  # takes_history_lengths, and nothing inside it
     for cls in (A.TwoTowerWithUserHistoryEncoder, A.TwoTowerWithDebiasing, A.TwoTowerWithPositionDebiasedWeights,
                 A.TwoTowerWithUserDebiasedWeights, A.TwoTowerPlusLightRanker):
-        assert "remove_accidental_hits" in own(cls.train_forward.__wrapped__), cls
-    with pytest.raises(TypeError, match="at most"):
+        assert "remove_accidental_hits" in own(cls.train_forward), cls
+    with pytest.raises(TypeError):
         ops.InBatchSoftmaxCE.forward(None, 1, 2, 3, 4, 5, 6, 7)
 
 
-def test_wrapper_keywords_are_bound_per_call_and_not_inherited():
+def test_remove_accidental_hits_is_bound_per_call_and_not_inherited():
+    """train_forward hands the candidate block's ids to compute_training_loss exactly when THIS call asks for the mask: a
+    call without the keyword, or with False, passes no `item_id`, whatever the call before it did."""
+    import two_tower_models_amd as A
     from two_tower_models_amd import two_tower_base_retrieval as B
     seen = []
+    u, v = torch.arange(24.0).reshape(3, 8), torch.ones(5, 8)
 
-    class M:
-        @B.takes_remove_accidental_hits
-        def train_forward(self, inner=None):
-            seen.append(B._REMOVE_HITS.get())
-            if inner is not None:
-                inner.train_forward()  # no keyword: the default, not the outer call's value
-                seen.append(B._REMOVE_HITS.get())
+    class M(A.TwoTowerBaseRetrieval):
+        def compute_user_embedding(self, user_id, user_features, user_history):
+            return u
 
-        @B.takes_item_id
-        def compute_training_loss(self):
-            return B._HIT_ITEM_ID.get()
+        def compute_item_embeddings(self, item_id, item_features):
+            return v
 
-    M().train_forward(M(), remove_accidental_hits=True)
-    assert seen == [True, False, True] and B._REMOVE_HITS.get() is False
-    assert M().compute_training_loss(item_id=7) == 7 and M().compute_training_loss() is None and B._HIT_ITEM_ID.get() is None
+        def compute_training_loss(self, user_embedding, item_embeddings, position, labels, **kw):
+            assert user_embedding is u and item_embeddings is v
+            seen.append(kw)
+            return torch.zeros(())
+
+    m = M(4, 10, 8, 4, 12, 8, 4, [1.0], A.BaselineMIPSModule(corpus_size=16, embedding_dim=8))
+    z = torch.zeros(3, dtype=torch.int64)
+    item_id, neg_id = torch.tensor([7, 3, 7]), torch.tensor([3, 11])
+    batch = (z, torch.zeros(3, 4), torch.zeros(3, 6, dtype=torch.int64), item_id, torch.zeros(3, 4), z, torch.zeros(3, 1))
+    neg = dict(negative_item_id=neg_id, negative_item_features=torch.zeros(2, 4))
+    assert float(m.train_forward(*batch, **neg, remove_accidental_hits=True)) == 0.0
+    assert list(seen[0]) == ["item_id"] and torch.equal(seen[0]["item_id"], torch.tensor([7, 3, 7, 3, 11]))
+    m.train_forward(*batch, **neg)
+    m.train_forward(*batch, **neg, remove_accidental_hits=False)
+    assert seen[1:] == [{}, {}]
+    m.train_forward(*batch, remove_accidental_hits=True)
+    assert list(seen[3]) == ["item_id"] and seen[3]["item_id"] is item_id
+    for name in ("_REMOVE_HITS", "_HIT_ITEM_ID", "takes_item_id", "takes_remove_accidental_hits"):
+        assert not hasattr(B, name), name
 
 
 def test_item_key_is_validated_before_any_device_work():

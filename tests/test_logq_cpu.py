@@ -69,15 +69,20 @@ def test_model_signatures_keep_the_reference_parameters_first():
                 A.TwoTowerWithPositionDebiasedWeights, A.TwoTowerWithUserDebiasedWeights, A.TwoTowerPlusLightRanker):
         sig = inspect.signature(cls.train_forward)
         names = list(sig.parameters)
-        assert names[:8] == ref_train and names[8:] == new_train, (cls.__name__, names)
+        assert names[:8] == ref_train and names[8:] == new_train + ["remove_accidental_hits"], (cls.__name__, names)
         assert all(sig.parameters[n].default is inspect.Parameter.empty for n in ref_train[1:])
         assert all(sig.parameters[n].default is None for n in new_train)
+        hits = sig.parameters["remove_accidental_hits"]
+        assert hits.kind is inspect.Parameter.KEYWORD_ONLY and hits.default is False
     sig = inspect.signature(A.TwoTowerBaseRetrieval.compute_training_loss)
-    assert list(sig.parameters) == ["self", "user_embedding", "item_embeddings", "position", "labels", "item_log_q"]
+    assert list(sig.parameters) == ["self", "user_embedding", "item_embeddings", "position", "labels", "item_log_q", "item_id"]
     assert sig.parameters["item_log_q"].default is None
+    assert sig.parameters["item_id"].kind is inspect.Parameter.KEYWORD_ONLY and sig.parameters["item_id"].default is None
     from two_tower_models_amd import ops
-    assert list(inspect.signature(ops.InBatchSoftmaxCE.forward).parameters)[1:] == ["U", "I", "diag_offset", "keep_logits", "item_bias"]
-    assert list(inspect.signature(ops.InBatchSoftmaxWeightedLoss.forward).parameters)[1:] == ["U", "I", "labels", "uvw", "item_bias"]
+    for fn, names in ((ops.InBatchSoftmaxCE.forward, ["U", "I", "diag_offset", "keep_logits", "item_bias", "item_key"]),
+                      (ops.InBatchSoftmaxWeightedLoss.forward, ["U", "I", "labels", "uvw", "item_bias", "item_key"])):
+        sig = inspect.signature(fn)
+        assert list(sig.parameters)[1:] == names and sig.parameters["item_key"].default is None
 
 
 def test_new_arguments_are_refused_where_they_are_not_implemented():

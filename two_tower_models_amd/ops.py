@@ -8,7 +8,6 @@ allocator, the autograd tape and the stream.
 from __future__ import annotations
 
 import ctypes as C
-import functools
 import os
 import weakref
 import warnings
@@ -950,22 +949,80 @@ def _item_key(item_key: Optional[torch.Tensor], I: torch.Tensor, what: str) -> O
     return item_key.detach().to(torch.int32).contiguous()  # no gradient flows to the keys
 
 
-def _takes_item_key(fn):
-    """Decorator of an autograd forward: one more trailing positional argument, `item_key`, behind `fn`'s own; it reaches
-    `fn` as `ctx.item_key_arg`.  `fn`'s own parameter list stays what introspection reports (functools.wraps, as
-    two_tower_base_retrieval.takes_history_lengths does for the models); the argument shows on the wrapper itself
-    (``inspect.signature(f, follow_wrapped=False)``)."""
-    own = fn.__code__.co_argcount  # ctx and fn's own inputs
+def _inbatch_ce_fwd(U, I, diag_offset, item_bias, item_key, du_unit=None, kept=None, loss_tail=None):
+    """One in-batch softmax forward -> (lse, ce), both [M], through the NARROWEST entry point for the form: with keys
+    tt_inbatch_ce_masked_fwd, with a term only tt_inbatch_ce_bias_fwd, else the plain call its optional outputs select.
+    `du_unit` [M, D]: also the user-side gradient up to its row factor.  `kept` (uint8, tt_inbatch_ce_logits_bytes): also the logits.
+    `loss_tail` = (labels or None, T, uvw, w, coef, loss): the weighted-mean loss head in the launch that finishes the forward."""
+    dev = U.device
+    M, D = U.shape
+    Nn = I.shape[0]
+    lib = N.load()
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    ce = torch.empty(M, dtype=torch.float32, device=dev)
+    pu, _, _, ldu = _f32_2d(U, "U")
+    pi, _, _, ldi = _f32_2d(I, "I")
+    head = (pu, ldu, pi, ldi, M, Nn, D, diag_offset)
+    rows = (lse.data_ptr(), ce.data_ptr())
+    logits = (N.ptr(kept), kept.numel() if kept is not None else 0)
+    tail = (None, 0, None, None, None, None)
+    if loss_tail is not None:
+        labels, T, uvw, w, coef, loss = loss_tail
+        tail = (N.ptr(labels), T, uvw.data_ptr(), w.data_ptr(), coef.data_ptr(), loss.data_ptr())
+    if item_key is not None:
+        ws = _ws(dev, lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D))
+        N.check(lib.tt_inbatch_ce_masked_fwd(*head, N.ptr(item_bias), item_key.data_ptr(), *rows, N.ptr(du_unit), D, *logits, *tail,
+                                             *ws, N.stream()), "tt_inbatch_ce_masked_fwd")
+    elif item_bias is not None:
+        ws = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
+        N.check(lib.tt_inbatch_ce_bias_fwd(*head, item_bias.data_ptr(), *rows, N.ptr(du_unit), D, *logits, *tail, *ws, N.stream()),
+                "tt_inbatch_ce_bias_fwd")
+    else:
+        ws = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
+        if loss_tail is not None:
+            N.check(lib.tt_inbatch_ce_fwd_du_loss(*head, *tail[:3], *rows, du_unit.data_ptr(), D, *tail[3:], *ws, N.stream()),
+                    "tt_inbatch_ce_fwd_du_loss")
+        elif kept is not None:
+            N.check(lib.tt_inbatch_ce_fwd_du_keep(*head, *rows, du_unit.data_ptr(), D, *logits, *ws, N.stream()),
+                    "tt_inbatch_ce_fwd_du_keep")
+        elif du_unit is not None:
+            N.check(lib.tt_inbatch_ce_fwd_du(*head, *rows, du_unit.data_ptr(), D, *ws, N.stream()), "tt_inbatch_ce_fwd_du")
+        else:
+            N.check(lib.tt_inbatch_ce_fwd(*head, *rows, *ws, N.stream()), "tt_inbatch_ce_fwd")
+    return lse, ce
 
-    @functools.wraps(fn)
-    def forward(ctx, *inputs, item_key: Optional[torch.Tensor] = None):
-        if len(inputs) > own:
-            raise TypeError(f"{fn.__qualname__}: at most {own} inputs (the last one item_key), got {len(inputs)}")
-        if len(inputs) == own:
-            inputs, item_key = inputs[:-1], inputs[-1]
-        ctx.item_key_arg = item_key
-        return fn(ctx, *inputs)
-    return forward
+
+def _inbatch_ce_item_side(U, I, diag_offset, item_bias, item_key, lse, coef, dU, dI, kept=None, kept16=None):
+    """dI (and, where `dU` is given -- the forward saved no du_unit --, dU) of one in-batch softmax.  `kept16`: the
+    split-fp16 pair ran forward (True: no logits buffer, the tiles are formed again); `kept`: the forward's logits (they
+    include the per-item term and the mask, if any); else the logits are recomputed, masked / with the term / plain."""
+    dev = U.device
+    M, D = U.shape
+    Nn = I.shape[0]
+    lib = N.load()
+    pu, _, _, ldu = _f32_2d(U, "U")
+    pi, _, _, ldi = _f32_2d(I, "I")
+    ws = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D) if (item_bias is None and item_key is None)
+             else lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D))  # (= the _bias_ calls' size)
+    head = (pu, ldu, pi, ldi, M, Nn, D, diag_offset)
+    grads = (lse.data_ptr(), coef.data_ptr(), N.ptr(dU), D, dI.data_ptr(), D, *ws, N.stream())
+    if kept16 is not None:  # the split-fp16 pair's backward
+        w16p, w16n = _ws(dev, lib.tt_ce16_workspace_bytes(M, Nn, D), "ce16")
+        if kept16 is True:  # (images formed again: other products may have used the workspace slot since the forward)
+            N.check(lib.tt_ce16_bwd_recompute(pu, D, pi, D, M, Nn, D, diag_offset, lse.data_ptr(), coef.data_ptr(), dI.data_ptr(), D,
+                                              w16p, w16n, 0, N.stream()), "tt_ce16_bwd_recompute")
+        else:
+            N.check(lib.tt_ce16_bwd_kept(pu, D, M, Nn, D, diag_offset, lse.data_ptr(), coef.data_ptr(), kept16.data_ptr(),
+                                         M * Nn * 4, dI.data_ptr(), D, w16p, w16n, N.stream()), "tt_ce16_bwd_kept")
+    elif kept is not None:
+        N.check(lib.tt_inbatch_ce_bwd_kept(pu, ldu, M, Nn, D, diag_offset, lse.data_ptr(), coef.data_ptr(), kept.data_ptr(),
+                                           kept.numel(), dI.data_ptr(), D, *ws, N.stream()), "tt_inbatch_ce_bwd_kept")
+    elif item_key is not None:
+        N.check(lib.tt_inbatch_ce_masked_bwd(*head, N.ptr(item_bias), item_key.data_ptr(), *grads), "tt_inbatch_ce_masked_bwd")
+    elif item_bias is not None:
+        N.check(lib.tt_inbatch_ce_bias_bwd(*head, item_bias.data_ptr(), *grads), "tt_inbatch_ce_bias_bwd")
+    else:
+        N.check(lib.tt_inbatch_ce_bwd(*head, *grads), "tt_inbatch_ce_bwd")
 
 
 class InBatchSoftmaxCE(torch.autograd.Function):
@@ -975,16 +1032,15 @@ class InBatchSoftmaxCE(torch.autograd.Function):
     column j != i + diag_offset whose key equals the positive's (accidental hits)."""
 
     @staticmethod
-    @_takes_item_key
-    def forward(ctx, U, I, diag_offset: int = 0, keep_logits: Optional[bool] = None, item_bias: Optional[torch.Tensor] = None):
+    def forward(ctx, U, I, diag_offset: int = 0, keep_logits: Optional[bool] = None, item_bias: Optional[torch.Tensor] = None,
+                item_key: Optional[torch.Tensor] = None):
         """`keep_logits`: write the [M, N] logits out in the forward so the item-side backward does not
         recompute them (3 instead of 4 logit-sized products, for M*N*4 B of HBM each way).  Default:
         only for wide negative sets (N >= 4 M, i.e. several ranks' items per user) -- at N = M the
         step is bound by the Adam sweep's HBM traffic and the extra bytes cost more than the MFMAs.
         `item_bias`: float32 [N], added to every logit of its column (the positive included) inside the product
         kernels; receives no gradient.  With it the fp32-MFMA kernels run (never the exploratory split-fp16 pair).
-        `item_key` (a sixth input, `apply(U, I, diag_offset, keep_logits, item_bias, item_key)`, see _takes_item_key):
-        int32 / int64 [N]; a column other than the positive's whose key equals the positive's is masked
+        `item_key`: int32 / int64 [N]; a column other than the positive's whose key equals the positive's is masked
         inside the product kernels, forward and backward (tt_inbatch_ce_masked_fwd / _bwd).  Same kernels' routing
         as with a term: never the split-fp16 pair."""
         dev = N.require_device(U, I)
@@ -993,29 +1049,23 @@ class InBatchSoftmaxCE(torch.autograd.Function):
         Nn = I.shape[0]
         lib = N.load()
         item_bias = _item_bias(item_bias, I, "InBatchSoftmaxCE")
-        item_key = _item_key(ctx.item_key_arg, I, "InBatchSoftmaxCE")
-        ctx.keyed = item_key is not None
-        if item_bias is not None or item_key is not None:
-            return InBatchSoftmaxCE._forward_biased(ctx, lib, dev, U, I, M, Nn, D, diag_offset, keep_logits, item_bias, item_key)
-        ctx.biased = False
-        lse = torch.empty(M, dtype=torch.float32, device=dev)
-        ce = torch.empty(M, dtype=torch.float32, device=dev)
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
-        pu, _, _, ldu = _f32_2d(U, "U")
-        pi, _, _, ldi = _f32_2d(I, "I")
+        item_key = _item_key(item_key, I, "InBatchSoftmaxCE")
         ctx.diag_offset = diag_offset
         ctx.kept = ctx.kept16 = None
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and ldu == D and ldi == D and ce16_usable(U, I) \
-                and 0 <= diag_offset <= Nn - M:
+        if item_bias is None and item_key is None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] \
+                and U.is_contiguous() and I.is_contiguous() and ce16_usable(U, I) and 0 <= diag_offset <= Nn - M:
+            lse = torch.empty(M, dtype=torch.float32, device=dev)
+            ce = torch.empty(M, dtype=torch.float32, device=dev)
             du_unit = torch.empty(M, D, dtype=torch.float32, device=dev)
             w16p, w16n = _ws(dev, lib.tt_ce16_workspace_bytes(M, Nn, D), "ce16")
             # no logits buffer unless asked for (_CE16_KEEP, the pair's first form): the backward forms the tiles again
             ctx.kept16 = torch.empty(M * Nn, dtype=torch.float32, device=dev) if _CE16_KEEP else True
-            N.check(lib.tt_ce16_fwd_du_keep(pu, D, pi, D, M, Nn, D, diag_offset, lse.data_ptr(), ce.data_ptr(), du_unit.data_ptr(), D,
-                                            ctx.kept16.data_ptr() if _CE16_KEEP else None, M * Nn * 4 if _CE16_KEEP else 0, w16p, w16n,
-                                            N.stream()), "tt_ce16_fwd_du_keep")
-            ctx.save_for_backward(U, I, lse, du_unit)
+            N.check(lib.tt_ce16_fwd_du_keep(U.data_ptr(), D, I.data_ptr(), D, M, Nn, D, diag_offset, lse.data_ptr(), ce.data_ptr(),
+                                            du_unit.data_ptr(), D, ctx.kept16.data_ptr() if _CE16_KEEP else None,
+                                            M * Nn * 4 if _CE16_KEEP else 0, w16p, w16n, N.stream()), "tt_ce16_fwd_du_keep")
+            ctx.save_for_backward(U, I, lse, du_unit, None, None)
             return ce
+        du_unit = None
         if ctx.needs_input_grad[0]:
             # training: the forward also accumulates E[i] = sum_j p_ij I_j, which IS the user-side
             # gradient up to the row factor -- the backward then only runs the item-side kernel
@@ -1025,133 +1075,39 @@ class InBatchSoftmaxCE(torch.autograd.Function):
                                                     "(csrc/ce_wide.hip) instead of the register-stationary kernels")
             if keep_logits is None:
                 keep_logits = Nn >= 4 * M
-            if keep_logits and ctx.needs_input_grad[1] and not kept_logits_supported(U, I):
-                note_generic("in-batch softmax CE backward (wide negative sets)",
-                             f"kept logits need D in {{32, 64, 128}}, N < 4 Mi and 16-B aligned rows; got D = {D}, N = {Nn}: "
-                             "the item-side backward recomputes the logits (4 instead of 3 logit-sized products)")
-            keep_logits = bool(keep_logits) and ctx.needs_input_grad[1] and kept_logits_supported(U, I)
-            if keep_logits:
-                zn = lib.tt_inbatch_ce_logits_bytes(M, Nn)
-                ctx.kept = torch.empty(zn, dtype=torch.uint8, device=dev)
-                N.check(lib.tt_inbatch_ce_fwd_du_keep(pu, ldu, pi, ldi, M, Nn, D, diag_offset, lse.data_ptr(),
-                                                      ce.data_ptr(), du_unit.data_ptr(), D, ctx.kept.data_ptr(), zn,
-                                                      wsp, wsn, N.stream()), "tt_inbatch_ce_fwd_du_keep")
-            else:
-                N.check(lib.tt_inbatch_ce_fwd_du(pu, ldu, pi, ldi, M, Nn, D, diag_offset, lse.data_ptr(), ce.data_ptr(),
-                                                 du_unit.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_fwd_du")
-            ctx.save_for_backward(U, I, lse, du_unit)
-            return ce
-        N.check(lib.tt_inbatch_ce_fwd(pu, ldu, pi, ldi, M, Nn, D, diag_offset, lse.data_ptr(), ce.data_ptr(),
-                                      wsp, wsn, N.stream()), "tt_inbatch_ce_fwd")
-        ctx.save_for_backward(U, I, lse)
-        return ce
-
-    @staticmethod
-    def _forward_biased(ctx, lib, dev, U, I, M, Nn, D, diag_offset, keep_logits, item_bias, item_key=None):
-        """The same three forms (plain / + du_unit / + kept logits) through tt_inbatch_ce_bias_fwd, or with keys through
-        tt_inbatch_ce_masked_fwd (the term may then be absent)."""
-        ctx.biased = item_bias is not None
-        ctx.diag_offset = diag_offset
-        ctx.kept = ctx.kept16 = None
-        lse = torch.empty(M, dtype=torch.float32, device=dev)
-        ce = torch.empty(M, dtype=torch.float32, device=dev)
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
-        pu, _, _, ldu = _f32_2d(U, "U")
-        pi, _, _, ldi = _f32_2d(I, "I")
-        du_unit, zp, zn = None, None, 0
-        if ctx.needs_input_grad[0]:
-            du_unit = torch.empty(M, D, dtype=torch.float32, device=dev)
-            if D > 128:
-                note_generic("in-batch softmax CE", f"D = {D} > 128: logits materialised per row chunk + library GEMMs "
-                                                    "(csrc/ce_wide.hip) instead of the register-stationary kernels")
-            if keep_logits is None:
-                keep_logits = Nn >= 4 * M
-            if keep_logits and ctx.needs_input_grad[1] and not kept_logits_supported(U, I):
-                note_generic("in-batch softmax CE backward (wide negative sets)",
-                             f"kept logits need D in {{32, 64, 128}}, N < 4 Mi and 16-B aligned rows; got D = {D}, N = {Nn}: "
-                             "the item-side backward recomputes the logits (4 instead of 3 logit-sized products)")
-            if bool(keep_logits) and ctx.needs_input_grad[1] and kept_logits_supported(U, I):
-                zn = lib.tt_inbatch_ce_logits_bytes(M, Nn)
-                ctx.kept = torch.empty(zn, dtype=torch.uint8, device=dev)
-                zp = ctx.kept.data_ptr()
-        if item_key is not None:
-            N.check(lib.tt_inbatch_ce_masked_fwd(pu, ldu, pi, ldi, M, Nn, D, diag_offset, N.ptr(item_bias), item_key.data_ptr(),
-                                                 lse.data_ptr(), ce.data_ptr(), N.ptr(du_unit), D, zp, zn, None, 0, None, None, None,
-                                                 None, wsp, wsn, N.stream()), "tt_inbatch_ce_masked_fwd")
-        else:
-            N.check(lib.tt_inbatch_ce_bias_fwd(pu, ldu, pi, ldi, M, Nn, D, diag_offset, item_bias.data_ptr(), lse.data_ptr(), ce.data_ptr(),
-                                               N.ptr(du_unit), D, zp, zn, None, 0, None, None, None, None, wsp, wsn, N.stream()),
-                    "tt_inbatch_ce_bias_fwd")
-        ctx.save_for_backward(U, I, lse, *[t for t in (item_bias, item_key, du_unit) if t is not None])
+            if keep_logits and ctx.needs_input_grad[1]:
+                if kept_logits_supported(U, I):
+                    ctx.kept = torch.empty(lib.tt_inbatch_ce_logits_bytes(M, Nn), dtype=torch.uint8, device=dev)
+                else:
+                    note_generic("in-batch softmax CE backward (wide negative sets)",
+                                 f"kept logits need D in {{32, 64, 128}}, N < 4 Mi and 16-B aligned rows; got D = {D}, N = {Nn}: "
+                                 "the item-side backward recomputes the logits (4 instead of 3 logit-sized products)")
+        lse, ce = _inbatch_ce_fwd(U, I, diag_offset, item_bias, item_key, du_unit, ctx.kept)
+        ctx.save_for_backward(U, I, lse, du_unit, item_bias, item_key)
         return ce
 
     @staticmethod
     def backward(ctx, d_ce):
-        saved = ctx.saved_tensors
-        U, I, lse = saved[:3]
-        item_bias = item_key = None
-        if ctx.biased:
-            item_bias, saved = saved[3], saved[:3] + saved[4:]
-        if ctx.keyed:
-            item_key, saved = saved[3], saved[:3] + saved[4:]
-        du_unit = saved[3] if len(saved) > 3 else None
-        dev = U.device
+        U, I, lse, du_unit, item_bias, item_key = ctx.saved_tensors
         M, D = U.shape
-        Nn = I.shape[0]
-        lib = N.load()
         coef = d_ce.contiguous()
-        dU = torch.empty(M, D, dtype=torch.float32, device=dev)
+        dU = torch.empty(M, D, dtype=torch.float32, device=U.device)
         if du_unit is not None:
-            N.check(lib.tt_scale_rows(du_unit.data_ptr(), D, coef.data_ptr(), M, D, dU.data_ptr(), D, N.stream()), "tt_scale_rows")
-        dI = torch.empty(Nn, D, dtype=torch.float32, device=dev)
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D) if (item_bias is None and item_key is None)
-                       else lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D))  # (= the _bias_ calls' size)
-        pu, _, _, ldu = _f32_2d(U, "U")
-        pi, _, _, ldi = _f32_2d(I, "I")
+            N.check(N.load().tt_scale_rows(du_unit.data_ptr(), D, coef.data_ptr(), M, D, dU.data_ptr(), D, N.stream()), "tt_scale_rows")
+        dI = torch.empty(I.shape[0], D, dtype=torch.float32, device=U.device)
         before = None
         if held_sweeps:  # a table sweep waits for this kernel to be in the queue: see DenseExactAdam._begin_overlapped
             before = torch.cuda.Event()
             before.record()
         try:
-            return InBatchSoftmaxCE._item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn,
-                                               item_bias, item_key)
+            _inbatch_ce_item_side(U, I, ctx.diag_offset, item_bias, item_key, lse, coef, dU if du_unit is None else None, dI,
+                                  ctx.kept, ctx.kept16)
         finally:
             if before is not None:
                 _release_held_sweeps(before)
-
-    @staticmethod
-    def _item_side(ctx, lib, dev, M, Nn, D, pu, ldu, pi, ldi, lse, coef, du_unit, dU, dI, wsp, wsn, item_bias=None, item_key=None):
-        # every path returns SIX entries, one per input `apply` can be given (U, I, diag_offset, keep_logits, item_bias,
-        # item_key): autograd wants at least as many as it was given and ignores trailing None beyond them
-        if ctx.kept16 is not None:  # the split-fp16 pair's backward
-            w16p, w16n = _ws(dev, lib.tt_ce16_workspace_bytes(M, Nn, D), "ce16")
-            if ctx.kept16 is True:  # (images formed again: other products may have used the workspace slot since the forward)
-                N.check(lib.tt_ce16_bwd_recompute(pu, D, pi, D, M, Nn, D, ctx.diag_offset, lse.data_ptr(), coef.data_ptr(), dI.data_ptr(), D,
-                                                  w16p, w16n, 0, N.stream()), "tt_ce16_bwd_recompute")
-            else:
-                N.check(lib.tt_ce16_bwd_kept(pu, D, M, Nn, D, ctx.diag_offset, lse.data_ptr(), coef.data_ptr(), ctx.kept16.data_ptr(),
-                                             M * Nn * 4, dI.data_ptr(), D, w16p, w16n, N.stream()), "tt_ce16_bwd_kept")
-            ctx.kept16 = None
-            return dU, dI, None, None, None, None
-        if ctx.kept is not None:  # item side from the logits the forward kept (they include the per-item term and the mask, if any)
-            N.check(lib.tt_inbatch_ce_bwd_kept(pu, ldu, M, Nn, D, ctx.diag_offset, lse.data_ptr(), coef.data_ptr(),
-                                               ctx.kept.data_ptr(), ctx.kept.numel(), dI.data_ptr(), D, wsp, wsn,
-                                               N.stream()), "tt_inbatch_ce_bwd_kept")
-            ctx.kept = None
-            return dU, dI, None, None, None, None
-        if item_key is not None:
-            N.check(lib.tt_inbatch_ce_masked_bwd(pu, ldu, pi, ldi, M, Nn, D, ctx.diag_offset, N.ptr(item_bias), item_key.data_ptr(),
-                                                 lse.data_ptr(), coef.data_ptr(), None if du_unit is not None else dU.data_ptr(), D,
-                                                 dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_masked_bwd")
-            return dU, dI, None, None, None, None
-        if item_bias is not None:
-            N.check(lib.tt_inbatch_ce_bias_bwd(pu, ldu, pi, ldi, M, Nn, D, ctx.diag_offset, item_bias.data_ptr(), lse.data_ptr(),
-                                               coef.data_ptr(), None if du_unit is not None else dU.data_ptr(), D,
-                                               dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bias_bwd")
-            return dU, dI, None, None, None, None
-        N.check(lib.tt_inbatch_ce_bwd(pu, ldu, pi, ldi, M, Nn, D, ctx.diag_offset, lse.data_ptr(),
-                                      coef.data_ptr(), None if du_unit is not None else dU.data_ptr(), D,
-                                      dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bwd")
+        ctx.kept = ctx.kept16 = None
+        # SIX entries, one per input `apply` can be given (U, I, diag_offset, keep_logits, item_bias, item_key): autograd
+        # wants at least as many as it was given and ignores trailing None beyond them
         return dU, dI, None, None, None, None
 
 
@@ -1233,18 +1189,15 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
     starts with ONE launch that forms dL/dce * g and dU (tt_scale_rows_g) instead of an elementwise multiply and a row
     scaling.  Same values as the two ops, bit for bit; two launches fewer on the step's critical path.
     `item_bias` (float32 [N], optional): the per-item logit term of InBatchSoftmaxCE; no gradient.
-    `item_key` (int32 / int64 [N], optional sixth input, see _takes_item_key): accidental hits masked as in InBatchSoftmaxCE; no gradient."""
+    `item_key` (int32 / int64 [N], optional): accidental hits masked as in InBatchSoftmaxCE; no gradient."""
 
     @staticmethod
-    @_takes_item_key
-    def forward(ctx, U, I, labels, uvw, item_bias: Optional[torch.Tensor] = None):
+    def forward(ctx, U, I, labels, uvw, item_bias: Optional[torch.Tensor] = None, item_key: Optional[torch.Tensor] = None):
         dev = N.require_device(U, I, labels, uvw)
         U, I, uvw = _rowmajor(U), _rowmajor(I), uvw.contiguous()
         M, D = U.shape
-        Nn = I.shape[0]
         item_bias = _item_bias(item_bias, I, "InBatchSoftmaxWeightedLoss")
-        item_key = _item_key(ctx.item_key_arg, I, "InBatchSoftmaxWeightedLoss")
-        ctx.biased, ctx.keyed = item_bias is not None, item_key is not None
+        item_key = _item_key(item_key, I, "InBatchSoftmaxWeightedLoss")
         T = 1
         if labels is not None:
             labels = _labels_f32(labels, "InBatchSoftmaxWeightedLoss")
@@ -1252,68 +1205,25 @@ class InBatchSoftmaxWeightedLoss(torch.autograd.Function):
         if D > 128:
             note_generic("in-batch softmax CE", f"D = {D} > 128: logits materialised per row chunk + library GEMMs "
                                                 "(csrc/ce_wide.hip) instead of the register-stationary kernels")
-        lib = N.load()
-        lse = torch.empty(M, dtype=torch.float32, device=dev)
-        ce = torch.empty(M, dtype=torch.float32, device=dev)
         w = torch.empty(M, dtype=torch.float32, device=dev)
         coef = torch.empty(M, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         du_unit = torch.empty(M, D, dtype=torch.float32, device=dev)
-        pu, _, _, ldu = _f32_2d(U, "U")
-        pi, _, _, ldi = _f32_2d(I, "I")
-        if item_key is not None:
-            wsp, wsn = _ws(dev, lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D))
-            N.check(lib.tt_inbatch_ce_masked_fwd(pu, ldu, pi, ldi, M, Nn, D, 0, N.ptr(item_bias), item_key.data_ptr(), lse.data_ptr(),
-                                                 ce.data_ptr(), du_unit.data_ptr(), D, None, 0, N.ptr(labels), T, uvw.data_ptr(),
-                                                 w.data_ptr(), coef.data_ptr(), loss.data_ptr(), wsp, wsn, N.stream()),
-                    "tt_inbatch_ce_masked_fwd")
-            ctx.save_for_backward(U, I, lse, du_unit, coef, *[t for t in (item_bias, item_key) if t is not None])
-            return loss
-        if item_bias is not None:
-            wsp, wsn = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
-            N.check(lib.tt_inbatch_ce_bias_fwd(pu, ldu, pi, ldi, M, Nn, D, 0, item_bias.data_ptr(), lse.data_ptr(), ce.data_ptr(),
-                                               du_unit.data_ptr(), D, None, 0, N.ptr(labels), T, uvw.data_ptr(), w.data_ptr(),
-                                               coef.data_ptr(), loss.data_ptr(), wsp, wsn, N.stream()), "tt_inbatch_ce_bias_fwd")
-            ctx.save_for_backward(U, I, lse, du_unit, coef, item_bias)
-            return loss
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
-        N.check(lib.tt_inbatch_ce_fwd_du_loss(pu, ldu, pi, ldi, M, Nn, D, 0, N.ptr(labels), T, uvw.data_ptr(), lse.data_ptr(),
-                                              ce.data_ptr(), du_unit.data_ptr(), D, w.data_ptr(), coef.data_ptr(), loss.data_ptr(),
-                                              wsp, wsn, N.stream()), "tt_inbatch_ce_fwd_du_loss")
-        ctx.save_for_backward(U, I, lse, du_unit, coef)
+        lse, _ = _inbatch_ce_fwd(U, I, 0, item_bias, item_key, du_unit, None, (labels, T, uvw, w, coef, loss))
+        ctx.save_for_backward(U, I, lse, du_unit, item_bias, item_key, coef)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        U, I, lse, du_unit, coef = ctx.saved_tensors[:5]
-        item_bias = ctx.saved_tensors[5] if ctx.biased else None
-        item_key = ctx.saved_tensors[-1] if ctx.keyed else None
-        dev = U.device
+        U, I, lse, du_unit, item_bias, item_key, coef = ctx.saved_tensors
         M, D = U.shape
-        Nn = I.shape[0]
-        lib = N.load()
         g = g.contiguous()
-        dU = torch.empty(M, D, dtype=torch.float32, device=dev)
-        coef_g = torch.empty(M, dtype=torch.float32, device=dev)
-        N.check(lib.tt_scale_rows_g(du_unit.data_ptr(), D, coef.data_ptr(), g.data_ptr(), M, D, dU.data_ptr(), D, coef_g.data_ptr(),
-                                    N.stream()), "tt_scale_rows_g")
-        dI = torch.empty(Nn, D, dtype=torch.float32, device=dev)
-        pu, _, _, ldu = _f32_2d(U, "U")
-        pi, _, _, ldi = _f32_2d(I, "I")
-        if item_key is not None:
-            wsp, wsn = _ws(dev, lib.tt_inbatch_ce_masked_workspace_bytes(M, Nn, D))
-            N.check(lib.tt_inbatch_ce_masked_bwd(pu, ldu, pi, ldi, M, Nn, D, 0, N.ptr(item_bias), item_key.data_ptr(), lse.data_ptr(),
-                                                 coef_g.data_ptr(), None, D, dI.data_ptr(), D, wsp, wsn, N.stream()),
-                    "tt_inbatch_ce_masked_bwd")
-            return dU, dI, None, None, None, None
-        if item_bias is not None:
-            wsp, wsn = _ws(dev, lib.tt_inbatch_ce_bias_workspace_bytes(M, Nn, D))
-            N.check(lib.tt_inbatch_ce_bias_bwd(pu, ldu, pi, ldi, M, Nn, D, 0, item_bias.data_ptr(), lse.data_ptr(), coef_g.data_ptr(),
-                                               None, D, dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bias_bwd")
-            return dU, dI, None, None, None, None
-        wsp, wsn = _ws(dev, lib.tt_inbatch_ce_workspace_bytes(M, Nn, D))
-        N.check(lib.tt_inbatch_ce_bwd(pu, ldu, pi, ldi, M, Nn, D, 0, lse.data_ptr(), coef_g.data_ptr(), None, D,
-                                      dI.data_ptr(), D, wsp, wsn, N.stream()), "tt_inbatch_ce_bwd")
+        dU = torch.empty(M, D, dtype=torch.float32, device=U.device)
+        coef_g = torch.empty(M, dtype=torch.float32, device=U.device)
+        N.check(N.load().tt_scale_rows_g(du_unit.data_ptr(), D, coef.data_ptr(), g.data_ptr(), M, D, dU.data_ptr(), D,
+                                         coef_g.data_ptr(), N.stream()), "tt_scale_rows_g")
+        dI = torch.empty(I.shape[0], D, dtype=torch.float32, device=U.device)
+        _inbatch_ce_item_side(U, I, 0, item_bias, item_key, lse, coef_g, None, dI)
         return dU, dI, None, None, None, None
 
 

@@ -17,7 +17,6 @@ below stays overridable.
 from __future__ import annotations
 
 import contextlib
-import contextvars
 import functools
 from typing import List, Optional, Tuple
 
@@ -43,45 +42,6 @@ def takes_history_lengths(fn):
             return fn(self, *args, **kwargs)
         with self._history_lengths(user_history_lengths):
             return fn(self, *args, **kwargs)
-    return call
-
-
-# The two values the wrappers below hand to the wrapped bodies.  Context variables, not attributes of the module: each call
-# binds its own value for exactly its own duration (set / reset by token), so nested calls, several models and threads do not
-# see each other's; a call WITHOUT the keyword binds the default, it does not inherit an outer call's.
-_REMOVE_HITS = contextvars.ContextVar("tt_remove_accidental_hits", default=False)
-_HIT_ITEM_ID = contextvars.ContextVar("tt_hit_item_id", default=None)
-
-
-def takes_remove_accidental_hits(fn):
-    """Method decorator of ``train_forward``, in the manner of `takes_history_lengths`: the keyword
-    ``remove_accidental_hits=False`` behind ``fn``'s own parameters (keyword-only).  The wrapped body cannot declare it --
-    its parameter list is the reference's plus this package's earlier keywords, and stays what introspection reports -- so the
-    wrapper binds it for the duration of the call (`_REMOVE_HITS`) and the body reads it there."""
-    @functools.wraps(fn)
-    def call(self, *args, remove_accidental_hits: bool = False, **kwargs):
-        if not remove_accidental_hits and not _REMOVE_HITS.get():
-            return fn(self, *args, **kwargs)  # nothing to bind: the default is what the body would read
-        token = _REMOVE_HITS.set(bool(remove_accidental_hits))
-        try:
-            return fn(self, *args, **kwargs)
-        finally:
-            _REMOVE_HITS.reset(token)
-    return call
-
-
-def takes_item_id(fn):
-    """Method decorator of ``compute_training_loss``: the keyword ``item_id=None`` (one id per item row: the keys of the
-    accidental-hit mask) behind ``fn``'s own parameters, bound for the duration of the call (`_HIT_ITEM_ID`)."""
-    @functools.wraps(fn)
-    def call(self, *args, item_id: Optional[torch.Tensor] = None, **kwargs):
-        if item_id is None and _HIT_ITEM_ID.get() is None:
-            return fn(self, *args, **kwargs)
-        token = _HIT_ITEM_ID.set(item_id)
-        try:
-            return fn(self, *args, **kwargs)
-        finally:
-            _HIT_ITEM_ID.reset(token)
     return call
 
 
@@ -328,7 +288,6 @@ class TwoTowerBaseRetrieval(nn.Module):
         """Identity hook (ref :251-277); subclasses return (debiased value, extra loss)."""
         return net_user_value, 0
 
-    @takes_item_id
     def compute_training_loss(
         self,
         user_embedding: torch.Tensor,  # [B, DI]
@@ -336,6 +295,8 @@ class TwoTowerBaseRetrieval(nn.Module):
         position: torch.Tensor,  # [B]
         labels: torch.Tensor,  # [B, T]
         item_log_q: Optional[torch.Tensor] = None,  # [N], N = item_embeddings.shape[0] >= B
+        *,
+        item_id: Optional[torch.Tensor] = None,  # [N]
     ) -> torch.Tensor:
         """In-batch softmax loss weighted by normalised net user value (ref :279-347).
         The [B, B] logits are never materialised.
@@ -345,12 +306,11 @@ class TwoTowerBaseRetrieval(nn.Module):
         sampling-bias correction ref :289-295 names as missing (Yi et al. 2019, eq. 3).  ``item_embeddings`` may carry
         extra rows behind the batch's own B (mixed negatives): the positive of user i stays item row i.
 
-        ``item_id`` (keyword from `takes_item_id`; int32 / int64, one id per item row, [N];
+        ``item_id`` (keyword-only; int32 / int64, one id per item row, [N];
         ``train_forward(remove_accidental_hits=True)`` passes it):
         accidental hits are removed -- a column j != i that holds the same item id as user i's positive takes no part
         in row i's softmax, forward and backward (TensorFlow Recommenders' ``remove_accidental_hits``; the companion of the
         log-Q correction in Yi et al. 2019).  Ids are compared as 32-bit values."""
-        item_id = _HIT_ITEM_ID.get()
         if self._sharded():
             if item_log_q is not None or item_embeddings.shape[0] != user_embedding.shape[0]:
                 raise NotImplementedError("log-Q correction / extra negatives are not implemented for row-sharded models")
@@ -369,13 +329,8 @@ class TwoTowerBaseRetrieval(nn.Module):
             lab = labels if weighted else None
             if ops.fused_loss_supported(user_embedding, item_embeddings, lab, self.user_value_weights, item_bias, item_id):
                 # the loss head inside the launch that finishes the logits forward (one op, two launches fewer)
-                if item_id is not None:
-                    return ops.InBatchSoftmaxWeightedLoss.apply(user_embedding, item_embeddings, lab, self.user_value_weights,
-                                                                item_bias, item_id)
-                if item_bias is not None:
-                    return ops.InBatchSoftmaxWeightedLoss.apply(user_embedding, item_embeddings, lab, self.user_value_weights,
-                                                                item_bias)
-                return ops.InBatchSoftmaxWeightedLoss.apply(user_embedding, item_embeddings, lab, self.user_value_weights)
+                return ops.InBatchSoftmaxWeightedLoss.apply(user_embedding, item_embeddings, lab, self.user_value_weights,
+                                                            item_bias, item_id)
             row_ce = self._row_ce(user_embedding, item_embeddings, item_bias, item_id)  # [B]
             return ops.WeightedMeanLoss.apply(row_ce, lab, self.user_value_weights)
         row_ce = self._row_ce(user_embedding, item_embeddings, item_bias, item_id)  # [B]
@@ -383,11 +338,7 @@ class TwoTowerBaseRetrieval(nn.Module):
 
     @staticmethod
     def _row_ce(user_embedding, item_embeddings, item_bias, item_key=None) -> torch.Tensor:
-        if item_key is not None:
-            return ops.InBatchSoftmaxCE.apply(user_embedding, item_embeddings, 0, None, item_bias, item_key)
-        if item_bias is None:
-            return ops.InBatchSoftmaxCE.apply(user_embedding, item_embeddings, 0)
-        return ops.InBatchSoftmaxCE.apply(user_embedding, item_embeddings, 0, None, item_bias)
+        return ops.InBatchSoftmaxCE.apply(user_embedding, item_embeddings, 0, None, item_bias, item_key)
 
     def _loss_head(self, row_ce, labels, position, user_embedding) -> torch.Tensor:
         """General loss head: exactly the reference's expressions on [B]-sized tensors (ref :322-345), so every
@@ -476,7 +427,6 @@ class TwoTowerBaseRetrieval(nn.Module):
             opt.begin_step(plan, hold_sweep=hold)
 
     @takes_history_lengths
-    @takes_remove_accidental_hits
     def train_forward(
         self,
         user_id: torch.Tensor,  # [B]
@@ -490,6 +440,8 @@ class TwoTowerBaseRetrieval(nn.Module):
         negative_item_id: Optional[torch.Tensor] = None,  # [Bn]
         negative_item_features: Optional[torch.Tensor] = None,  # [Bn, II]
         negative_log_q: Optional[torch.Tensor] = None,  # [Bn]
+        *,
+        remove_accidental_hits: bool = False,
     ) -> torch.Tensor:
         """Scalar training loss with an autograd graph (ref :349-394).
 
@@ -500,8 +452,8 @@ class TwoTowerBaseRetrieval(nn.Module):
         positives stay on the leading diagonal, the extra rows get item-tower and table-row gradients like any other
         item); ``negative_log_q`` -- their log sampling probabilities (needed whenever ``item_log_q`` is given).
 
-        ``remove_accidental_hits`` (keyword from `takes_remove_accidental_hits`; default False: the reference's loss) -- another row of the batch, or an extra negative,
-        that holds the same item id as a user's positive is not counted as a negative for that user (see
+        ``remove_accidental_hits`` (keyword-only; default False: the reference's loss) -- another row of the batch, or an
+        extra negative, that holds the same item id as a user's positive is not counted as a negative for that user (see
         compute_training_loss).  The ids that key the mask are the candidate block's, batch items then extra negatives.
 
         One more keyword comes from the `takes_history_lengths` decorator:
@@ -513,7 +465,6 @@ class TwoTowerBaseRetrieval(nn.Module):
         if any(t is not None for t in (item_log_q, negative_item_id, negative_item_features, negative_log_q)):
             item_id, item_features, item_log_q = self._with_negatives(
                 item_id, item_features, item_log_q, negative_item_id, negative_item_features, negative_log_q)
-        remove_accidental_hits = _REMOVE_HITS.get()
         if remove_accidental_hits:
             if self._sharded():
                 raise NotImplementedError("train_forward: remove_accidental_hits is not implemented for row-sharded models "

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 from . import _native as N
 from . import ops
 from .baseline_mips_module import BaselineMIPSModule
-from .two_tower_base_retrieval import _REMOVE_HITS, takes_history_lengths, takes_remove_accidental_hits
+from .two_tower_base_retrieval import takes_history_lengths
 from .two_tower_with_debiasing import TwoTowerWithDebiasing
 
 _WEIGHT_MIN = 1.0e-6  # ref :282-284
@@ -132,11 +132,10 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
 
     # ------------------------------------------------------------------ training
     @takes_history_lengths
-    @takes_remove_accidental_hits
     def train_forward(self, user_id: torch.Tensor, user_features: torch.Tensor, user_history: torch.Tensor,
                       item_id: torch.Tensor, item_features: torch.Tensor, position: torch.Tensor,
                       labels: torch.Tensor, item_log_q=None, negative_item_id=None, negative_item_features=None,
-                      negative_log_q=None) -> torch.Tensor:
+                      negative_log_q=None, *, remove_accidental_hits: bool = False) -> torch.Tensor:
         """MIPS term + light ranker term (ref :211-340).  No host synchronisation: GraphedTrainStep captures it.
         The log-Q / extra-negative keywords of TwoTowerBaseRetrieval.train_forward are refused: the ranker term scores
         the impressed item only and has no corrected form here.  ``user_history_lengths`` is refused as well
@@ -145,7 +144,6 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
             raise NotImplementedError("TwoTowerPlusLightRanker.train_forward: item_log_q / negative_* are not implemented "
                                       "for the light-ranker model")
         self._check_unsharded("train_forward")
-        remove_accidental_hits = _REMOVE_HITS.get()
         if remove_accidental_hits and self.item_id_embedding_arch.num_embeddings > 2 ** 31:
             raise ValueError("train_forward: remove_accidental_hits compares item ids as 32-bit values; "
                              f"item_id_hash_size = {self.item_id_embedding_arch.num_embeddings} > 2 ** 31")
@@ -158,7 +156,7 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
         """ref :256-296: in-batch softmax CE per row, weighted by the (debiased) net user value clamped at 1e-6 -- no
         division by the batch maximum here (module docstring)."""
         # [B], the [B, B] logits never written; item_key: accidental hits masked
-        row_ce = ops.InBatchSoftmaxCE.apply(u, v, 0) if item_key is None else ops.InBatchSoftmaxCE.apply(u, v, 0, None, None, item_key)
+        row_ce = ops.InBatchSoftmaxCE.apply(u, v, 0, None, None, item_key)
         net_user_value = torch.matmul(labels, self.user_value_weights)  # [B]
         net_user_value, additional_loss = self.debias_net_user_value(net_user_value, position, u)
         net_user_value = torch.clamp(net_user_value, min=_WEIGHT_MIN)
