@@ -888,6 +888,44 @@ int tt_light_ranker_rerank(const void* corpus, int dtype, int64_t C, const int64
                            const float* uvw, int64_t T, int64_t* out_ids /*[B, K]*/, float* out_vals,
                            int32_t* oob_flag, tt_stream_t stream);
 
+/* ---------------------------------------------------------------- row L2-normalise with a scale (cosine logits)
+ * The reference scores the raw dot product (ref:src/two_tower_base_retrieval.py:287 torch.matmul(user_embedding,
+ * item_embeddings.t())); this is the op that goes between the towers and that line so that the SAME logits kernels score
+ * cos(u, v) / tau:   cos(u, v) / tau = < (1/tau) u/||u|| , v/||v|| >.   It stands for
+ *   s * torch.nn.functional.normalize(x, p=2, dim=1, eps=eps),   s = exp(*log_scale)
+ * and its autograd.  Per row r of a row-major fp32 operand [rows, D] (row stride ld >= D):
+ *   tt_l2norm_fwd   inv[r] = 1 / max(||x_r||_2, eps);   y_r = (s * inv[r]) * x_r;   inv [rows] is saved for the backward
+ *   tt_l2norm_bwd   n = x_r * inv[r],  t = <n, dy_r>
+ *                     ||x_r|| >  eps:   dx_r = (s * inv[r]) * (dy_r - n * t)
+ *                     ||x_r|| <= eps:   dx_r = (s / eps) * dy_r            (the forward stored inv[r] = 1 / eps exactly)
+ *                   *d_log_scale = sum_r <dy_r, y_r> = sum_r s * t         (d/d log s of s * n; WRITTEN, not accumulated)
+ * `log_scale` is a DEVICE pointer to one float (log(1 / tau)), read by the kernel: no host synchronisation, so both calls can
+ * be captured in a hipGraph while the optimiser moves the value.  NULL: s = 1.  `d_log_scale` NULL (a fixed temperature, or
+ * an unscaled side): the sum is not formed at all -- no partial is stored, no finishing launch is made, `ws` may be NULL.
+ * Each call takes n_sides = 1 or 2 operands (a host array, as tt_tower_fwd does; D and eps are the same for both): a
+ * training step normalises the user rows (scaled) and the item rows (unscaled, possibly more of them) in one launch per
+ * direction.  A side with rows == 0 is a no-op for that side (a d_log_scale it names is still written: 0).
+ * Any D >= 1, any alignment: 16-byte aligned bases with ld % 4 == 0 and D % 4 == 0 take the float4 form (per side), anything
+ * else the scalar form.  x / y / dx / dy of a call must not overlap.
+ * Reductions: a row's sum is a wave's xor-butterfly; d_log_scale sums per-workgroup partials (4 rows each; `ws`:
+ * tt_l2norm_bwd_workspace_bytes(rows) bytes for EACH side that has a d_log_scale, summed) in a fixed order in a second
+ * one-workgroup launch.  No atomics: the same bits run to run and under graph replay.
+ * TT_E_BADARG before any HIP call, with a message: null `sides` or a null x / y / inv / dx / dy of a side with rows > 0,
+ * n_sides outside 1..2, D < 1, a row stride < D, rows < 0, eps <= 0 or not finite (or so small that 1 / eps is not), a
+ * workspace that is NULL or too small while a d_log_scale is asked for. */
+typedef struct {
+  const float* x; int64_t ldx; float* y; int64_t ldy; float* inv /*[rows]*/; int64_t rows;
+  const float* log_scale /*device, 1 float, or NULL*/;
+} tt_l2norm_fwd_side;
+typedef struct {
+  const float* x; int64_t ldx; const float* dy; int64_t lddy; const float* inv /*[rows]*/; float* dx; int64_t lddx; int64_t rows;
+  const float* log_scale /*device, 1 float, or NULL*/; float* d_log_scale /*device, 1 float, or NULL*/;
+} tt_l2norm_bwd_side;
+int tt_l2norm_fwd(const tt_l2norm_fwd_side* sides /*host*/, int32_t n_sides, int64_t D, float eps, tt_stream_t stream);
+int64_t tt_l2norm_bwd_workspace_bytes(int64_t rows);
+int tt_l2norm_bwd(const tt_l2norm_bwd_side* sides /*host*/, int32_t n_sides, int64_t D, float eps, void* ws, int64_t ws_bytes,
+                  tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,19 @@ class RouteServeJob(C.Structure):
                 ("dim", _i64), ("rows", _vp)]
 
 
+class L2NormFwdSide(C.Structure):
+    """tt_l2norm_fwd_side."""
+
+    _fields_ = [("x", _vp), ("ldx", _i64), ("y", _vp), ("ldy", _i64), ("inv", _vp), ("rows", _i64), ("log_scale", _vp)]
+
+
+class L2NormBwdSide(C.Structure):
+    """tt_l2norm_bwd_side."""
+
+    _fields_ = [("x", _vp), ("ldx", _i64), ("dy", _vp), ("lddy", _i64), ("inv", _vp), ("dx", _vp), ("lddx", _i64), ("rows", _i64),
+                ("log_scale", _vp), ("d_log_scale", _vp)]
+
+
 # name -> (restype, argtypes); mirrors include/tt_hotpath.h declaration by declaration
 SIGNATURES = {
     "tt_abi_version": (_int, []),
@@ -258,6 +271,9 @@ SIGNATURES = {
                                         _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "tt_light_ranker_rerank": (_int, [_vp, _int, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp,
                                       _i64, _vp, _vp, _vp, _vp]),
+    "tt_l2norm_fwd": (_int, [C.POINTER(L2NormFwdSide), _i32, _i64, C.c_float, _vp]),
+    "tt_l2norm_bwd_workspace_bytes": (_i64, [_i64]),
+    "tt_l2norm_bwd": (_int, [C.POINTER(L2NormBwdSide), _i32, _i64, C.c_float, _vp, _i64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

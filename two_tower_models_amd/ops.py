@@ -1159,6 +1159,90 @@ class WeightedMeanLoss(torch.autograd.Function):
         return coef * g, None, None
 
 
+# ----------------------------------------------------------------- cosine logits: row-normalise (csrc/l2norm.hip)
+L2NORM_EPS = 1e-12  # torch.nn.functional.normalize's default
+
+
+def _l2n_operand(t: torch.Tensor, name: str) -> Tuple[torch.Tensor, int, int, int]:
+    """(tensor, rows, D, ld): a strided row-major view goes to the kernel as it is (its scalar form takes any alignment);
+    only rows that overlap (a row stride below D) are copied."""
+    if t.dim() == 2 and t.size(0) > 1 and t.stride(0) < t.size(1):
+        t = t.contiguous()
+    _, rows, D, ld = _f32_2d(t, name)
+    return t, rows, D, ld
+
+
+def _l2n_log_scale(log_scale: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    if log_scale is None:
+        return None
+    if log_scale.dtype != torch.float32 or log_scale.numel() != 1:
+        raise TypeError(f"{name}: log_scale must be one float32 value on the device, got {tuple(log_scale.shape)} {log_scale.dtype}")
+    return log_scale
+
+
+class L2NormalizePair(torch.autograd.Function):
+    """(s * u / max(||u||, eps), v / max(||v||, eps)) row by row, s = exp(log_scale) read on the device (None: 1): the two
+    operands of the in-batch softmax for cosine logits, cos(u, v) / tau with log_scale = log(1 / tau) -- what
+    ``s * F.normalize(u, dim=1), F.normalize(v, dim=1)`` computes, in ONE launch per direction (tt_l2norm_fwd /
+    tt_l2norm_bwd, both operands as the two sides of the call).  u [B, D] and v [N, D] are float32 row-major views, any row
+    stride and alignment, taken as they are.  The gradient of log_scale is sum_r <d(s u^)_r, (s u^)_r>, summed in a fixed
+    order (the same bits every run); it is formed only when log_scale needs one."""
+
+    @staticmethod
+    def forward(ctx, u, v, log_scale: Optional[torch.Tensor] = None):
+        dev = N.require_device(u, v, log_scale)
+        log_scale = _l2n_log_scale(log_scale, "L2NormalizePair")
+        u, Mu, D, ldu = _l2n_operand(u, "L2NormalizePair: u")
+        v, Mv, Dv, ldv = _l2n_operand(v, "L2NormalizePair: v")
+        if D != Dv:
+            raise RuntimeError(f"L2NormalizePair: u [{Mu}, {D}] and v [{Mv}, {Dv}] differ in width")
+        yu = torch.empty(Mu, D, dtype=torch.float32, device=dev)
+        yv = torch.empty(Mv, D, dtype=torch.float32, device=dev)
+        inv = torch.empty(Mu + Mv, dtype=torch.float32, device=dev)
+        sides = (N.L2NormFwdSide * 2)()
+        sides[0] = N.L2NormFwdSide(u.data_ptr(), ldu, yu.data_ptr(), D, inv.data_ptr(), Mu, N.ptr(log_scale))
+        sides[1] = N.L2NormFwdSide(v.data_ptr(), ldv, yv.data_ptr(), D, inv.data_ptr() + 4 * Mu, Mv, None)
+        N.check(N.load().tt_l2norm_fwd(sides, 2, D, L2NORM_EPS, N.stream()), "tt_l2norm_fwd")
+        ctx.save_for_backward(u, v, inv, log_scale)
+        return yu, yv
+
+    @staticmethod
+    def backward(ctx, dyu, dyv):
+        u, v, inv, log_scale = ctx.saved_tensors
+        dev = u.device
+        (Mu, D), Mv = u.shape, v.shape[0]
+        dyu, _, _, lddyu = _l2n_operand(dyu, "L2NormalizePair: d(s u^)")
+        dyv, _, _, lddyv = _l2n_operand(dyv, "L2NormalizePair: d(v^)")
+        ldu = _f32_2d(u, "u")[3]
+        ldv = _f32_2d(v, "v")[3]
+        dxu = torch.empty(Mu, D, dtype=torch.float32, device=dev)
+        dxv = torch.empty(Mv, D, dtype=torch.float32, device=dev)
+        d_ls, ws, ws_bytes = None, None, 0
+        if log_scale is not None and ctx.needs_input_grad[2]:
+            d_ls = torch.empty_like(log_scale)
+            ws, ws_bytes = _ws(dev, N.load().tt_l2norm_bwd_workspace_bytes(Mu), "l2norm")
+        sides = (N.L2NormBwdSide * 2)()
+        sides[0] = N.L2NormBwdSide(u.data_ptr(), ldu, dyu.data_ptr(), lddyu, inv.data_ptr(), dxu.data_ptr(), D, Mu,
+                                   N.ptr(log_scale), N.ptr(d_ls))
+        sides[1] = N.L2NormBwdSide(v.data_ptr(), ldv, dyv.data_ptr(), lddyv, inv.data_ptr() + 4 * Mu, dxv.data_ptr(), D, Mv,
+                                   None, None)
+        N.check(N.load().tt_l2norm_bwd(sides, 2, D, L2NORM_EPS, ws, ws_bytes, N.stream()), "tt_l2norm_bwd")
+        return dxu, dxv, d_ls
+
+
+def l2_normalize(x: torch.Tensor, log_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x / max(||x||, eps) row by row (times exp(log_scale) when given): the no-grad, one-operand form of L2NormalizePair
+    that serving uses (the corpus rows at index time, the query rows at search time).  One tt_l2norm_fwd launch."""
+    dev = N.require_device(x, log_scale)
+    log_scale = _l2n_log_scale(log_scale, "l2_normalize")
+    x, M, D, ld = _l2n_operand(x.detach(), "l2_normalize: x")
+    y = torch.empty(M, D, dtype=torch.float32, device=dev)
+    inv = torch.empty(M, dtype=torch.float32, device=dev)
+    side = N.L2NormFwdSide(x.data_ptr(), ld, y.data_ptr(), D, inv.data_ptr(), M, N.ptr(log_scale))
+    N.check(N.load().tt_l2norm_fwd(C.byref(side), 1, D, L2NORM_EPS, N.stream()), "tt_l2norm_fwd")
+    return y
+
+
 # EXPLORATORY (DESIGN.md 5): InBatchSoftmaxCE through the split-fp16 pair (csrc/ce_f16x2.hip) where its shapes allow
 # (D = 128, M % 256 == 0, N % 1024 == 0, contiguous rows) -- fp32-grade results on the fp16 matrix pipe.  Never the default.
 _CE16_KEEP = False  # A/B (tests flip it): the split-fp16 pair with kept logits (its first form) instead of recomputed ones

@@ -207,6 +207,12 @@ def main(args):
         raise SystemExit("--min_history_len is not implemented with --world_size > 1 (row-sharded tables)")
     if min_len is not None and args.model == "base":
         raise SystemExit("--min_history_len needs a model with a history encoder (--model hist or debias)")
+    cosine = bool(getattr(args, "cosine", False))
+    learn_t = bool(getattr(args, "learn_temperature", False))
+    if learn_t and not cosine:
+        raise SystemExit("--learn_temperature needs --cosine")
+    if cosine and world > 1:
+        raise SystemExit("--cosine is not implemented with --world_size > 1 (row-sharded tables)")
     if world > 1:
         device, rank = _init_distributed(world)
     else:
@@ -227,6 +233,8 @@ def main(args):
     model = model.to(device)
     if world > 1:
         parallel.shard_model_(model)
+    if cosine:  # before the optimiser is built: a learned scale is one of its (dense) parameters
+        model.use_cosine_logits(temperature=getattr(args, "temperature", 0.05), learnable=learn_t)
     # every rank draws its own records (a different seed per rank; the tables' row blocks are seeded per block by
     # parallel.embedding, so ranks whose default generators start identical still hold different rows)
     dataset = DummyRecDataset(num_samples=max(args.num_samples // world, 1), num_users=args.num_users, num_items=args.num_items,
@@ -250,7 +258,8 @@ def main(args):
         else:
             avg_loss = train_one_epoch(model, dataloader, optimizer, device, candidates=candidates)
         dt = time.perf_counter() - t0
-        say(f"Epoch [{epoch + 1}/{args.num_epochs}] - Loss: {avg_loss:.4f}")
+        say(f"Epoch [{epoch + 1}/{args.num_epochs}] - Loss: {avg_loss:.4f}"
+            + (f" - temperature: {model.logit_temperature:.5f}" if learn_t else ""))
         stats.append({"epoch": epoch + 1, "loss": avg_loss, "seconds": dt, "pairs_per_s": len(dataset) * world / dt})
         if getattr(args, "report_throughput", False):
             say(f"  {len(dataset) * world / dt:,.0f} user-item pairs/s end to end (shuffle + batch slicing + step), "
@@ -334,6 +343,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --retrieve: leave each user's history items out of its top-K (model.forward(..., "
                         "exclude_history=True): the search runs at K + history length, one filter kernel keeps the first K "
                         "unseen items); without --retrieve it has no effect")
+    p.add_argument("--cosine", action="store_true",
+                   help="cosine logits: score cos(u, v) / temperature instead of the raw dot product (model.use_cosine_logits: "
+                        "both operands of the in-batch softmax are L2-normalised; --retrieve then serves the normalised corpus "
+                        "and scores are cosines)")
+    p.add_argument("--temperature", type=float, default=0.05, help="with --cosine: the temperature (its initial value when learned)")
+    p.add_argument("--learn_temperature", action="store_true",
+                   help="with --cosine: learn log(1 / temperature) with the other parameters (no clamp: bound it with the "
+                        "learning rate); the temperature is printed with every epoch line")
     p.add_argument("--lazy_adam", action="store_true",
                    help="value-exact deferred Adam: replay a row's zero-gradient steps when it is next needed")
     return p

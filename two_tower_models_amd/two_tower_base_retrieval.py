@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import contextlib
 import functools
+import math
 from typing import List, Optional, Tuple
 
 import torch
@@ -92,6 +93,49 @@ class TwoTowerBaseRetrieval(nn.Module):
         super()._apply(fn, *a, **kw)
         self.user_value_weights = fn(self.user_value_weights)
         return self
+
+    # ------------------------------------------------------------------ cosine logits
+    def use_cosine_logits(self, temperature: float = 0.05, learnable: bool = False) -> "TwoTowerBaseRetrieval":
+        """Score ``cos(u, v) / temperature`` instead of the reference's raw ``<u, v>``: training normalises the two operands
+        of the in-batch softmax (ops.L2NormalizePair; every option of the loss composes with it unchanged), `index_corpus`
+        stores normalised item rows and `forward` searches with the normalised query, so served scores are cosines.
+
+        Registers ``logit_log_scale`` = log(1 / temperature), float32 [1]: an ``nn.Parameter`` when ``learnable`` (a dense
+        parameter to DenseExactAdam), else a persistent buffer.  The learned scale is NOT clamped (CLIP clamps its own at
+        100): bound it with the learning-rate schedule or clamp ``logit_log_scale.data`` between steps.  Call this before the
+        optimiser or a GraphedTrainStep is built; until it is called nothing about the model changes (no attribute, the
+        same state_dict keys, the same launches, the same bits).  ``logit_temperature`` reads the current value."""
+        temperature = float(temperature)
+        if not (temperature > 0.0) or temperature == float("inf"):
+            raise ValueError(f"use_cosine_logits: temperature must be positive and finite, got {temperature}")
+        if hasattr(self, "logit_log_scale"):
+            raise ValueError("use_cosine_logits: already called on this model")
+        self._check_cosine_supported()
+        dev = self.item_tower_arch.weight.device
+        value = torch.full((1,), -math.log(temperature), dtype=torch.float32, device=dev)
+        if learnable:
+            self.logit_log_scale = nn.Parameter(value)
+        else:
+            self.register_buffer("logit_log_scale", value, persistent=True)
+        return self
+
+    def _check_cosine_supported(self) -> None:
+        if self._sharded():
+            raise NotImplementedError("cosine logits are not implemented for row-sharded models")
+
+    def _cosine(self) -> bool:
+        """True when `use_cosine_logits` was called; refuses, before any kernel, what the switch does not cover."""
+        if not hasattr(self, "logit_log_scale"):
+            return False
+        self._check_cosine_supported()
+        return True
+
+    @property
+    def logit_temperature(self) -> float:
+        """The current temperature, exp(-logit_log_scale), as a Python float (synchronises; not for the training step)."""
+        if not hasattr(self, "logit_log_scale"):
+            raise AttributeError("logit_temperature: use_cosine_logits was not called on this model")
+        return float(torch.exp(-self.logit_log_scale.detach().double()).item())
 
     # ------------------------------------------------------------------ user tower
     def get_user_embedding(self, user_id: torch.Tensor, user_features: torch.Tensor) -> torch.Tensor:
@@ -181,12 +225,15 @@ class TwoTowerBaseRetrieval(nn.Module):
         ITEM ids: `index_corpus` records which corpus row holds which item (``mips_module.row_item_id``); the returned
         values stay MIPS row indices, as in the reference.  Cost: the search at K + E plus one filter launch
         (BaselineMIPSModule.search)."""
+        cosine = self._cosine()
         exclude = self._exclusion_list(user_history, exclude_history, exclude_item_id)
         # (the result is an index tensor: nothing to differentiate.  Under no_grad the lookups are not recorded for the
         # optimiser's table step -- an inference call between two train steps, with or without the caller's own no_grad,
         # leaves the training bookkeeping alone, and a row-sharded model needs no optimiser to be served)
         with torch.no_grad():
             user_embedding = self.compute_user_embedding(user_id, user_features, user_history)
+            if cosine:  # unscaled: against the normalised corpus of index_corpus the scores are cosines
+                user_embedding = ops.l2_normalize(user_embedding)
         if type(self.mips_module).forward is BaselineMIPSModule.forward:
             # this package's module: the reference discards the scores and the [B, K, DI] rows (ref :246-248) -- do not
             # gather (row-sharded corpus: do not exchange) half a gigabyte of rows at B = 1024, K = 1000 to drop them
@@ -240,6 +287,7 @@ class TwoTowerBaseRetrieval(nn.Module):
         catalogue -- rows [lo, hi) = parallel.block_range(C, rank, world)[1:], any item ids -- and the model's
         mips_module becomes (or stays) row-sharded with that block; `forward()` then searches all blocks together.  When
         every rank's ids are rows it owns itself (the usual catalogue: item r = row r of the item table) no row travels."""
+        cosine = self._cosine()
         sharded = self._sharded()
         local_only = False
         if sharded:
@@ -267,6 +315,8 @@ class TwoTowerBaseRetrieval(nn.Module):
                 out[lo:hi] = self.compute_item_embeddings(item_id[lo:hi], item_features[lo:hi])
             else:
                 self.compute_item_embeddings(item_id.new_zeros(1), item_features.new_zeros(1, item_features.shape[1]))
+        if cosine:  # in fp32, BEFORE any conversion to bf16
+            out = ops.l2_normalize(out)
         if sharded:
             self.mips_module.set_corpus(out, bf16=bf16, block=True)  # becomes (or stays) row-sharded
         else:
@@ -312,12 +362,18 @@ class TwoTowerBaseRetrieval(nn.Module):
         in row i's softmax, forward and backward (TensorFlow Recommenders' ``remove_accidental_hits``; the companion of the
         log-Q correction in Yi et al. 2019).  Ids are compared as 32-bit values."""
         if self._sharded():
+            self._cosine()  # (refuses: cosine logits on a model that was sharded after the switch)
             if item_log_q is not None or item_embeddings.shape[0] != user_embedding.shape[0]:
                 raise NotImplementedError("log-Q correction / extra negatives are not implemented for row-sharded models")
             if item_id is not None:
                 raise NotImplementedError("remove_accidental_hits is not implemented for row-sharded models")
             return self._sharded_training_loss(user_embedding, item_embeddings, position, labels)
         item_bias = None if item_log_q is None else -item_log_q
+        # cosine logits (use_cosine_logits): ONLY the two operands of the logits change -- (s * u^, v^) in one launch; the
+        # loss heads and the debias hooks below keep seeing the tower's own `user_embedding`
+        logit_u, logit_i = user_embedding, item_embeddings
+        if self._cosine():
+            logit_u, logit_i = ops.L2NormalizePair.apply(user_embedding, item_embeddings, self.logit_log_scale)
         hook_is_identity = type(self).debias_net_user_value is TwoTowerBaseRetrieval.debias_net_user_value
         T = self.user_value_weights.numel()
         B = user_embedding.shape[0]
@@ -327,13 +383,13 @@ class TwoTowerBaseRetrieval(nn.Module):
         weighted = labels.dim() == 2 and labels.shape[1] == T and labels.shape[0] == B
         if hook_is_identity and ops.labels_fusable(labels) and (weighted or plain_mean):
             lab = labels if weighted else None
-            if ops.fused_loss_supported(user_embedding, item_embeddings, lab, self.user_value_weights, item_bias, item_id):
+            if ops.fused_loss_supported(logit_u, logit_i, lab, self.user_value_weights, item_bias, item_id):
                 # the loss head inside the launch that finishes the logits forward (one op, two launches fewer)
-                return ops.InBatchSoftmaxWeightedLoss.apply(user_embedding, item_embeddings, lab, self.user_value_weights,
+                return ops.InBatchSoftmaxWeightedLoss.apply(logit_u, logit_i, lab, self.user_value_weights,
                                                             item_bias, item_id)
-            row_ce = self._row_ce(user_embedding, item_embeddings, item_bias, item_id)  # [B]
+            row_ce = self._row_ce(logit_u, logit_i, item_bias, item_id)  # [B]
             return ops.WeightedMeanLoss.apply(row_ce, lab, self.user_value_weights)
-        row_ce = self._row_ce(user_embedding, item_embeddings, item_bias, item_id)  # [B]
+        row_ce = self._row_ce(logit_u, logit_i, item_bias, item_id)  # [B]
         return self._loss_head(row_ce, labels, position, user_embedding)
 
     @staticmethod
@@ -462,6 +518,7 @@ class TwoTowerBaseRetrieval(nn.Module):
         1 <= length <= H; the slots behind them are padding that takes no part in the encoder's attention, its mean
         pool or any gradient.  Padded ids must still be valid item ids (pad with 0).  A length outside [1, H] raises
         IndexError like an id outside its table.  The base model ignores it, as it ignores ``user_history``."""
+        self._cosine()  # (refuses, before any kernel, cosine logits on a model that was sharded after the switch)
         if any(t is not None for t in (item_log_q, negative_item_id, negative_item_features, negative_log_q)):
             item_id, item_features, item_log_q = self._with_negatives(
                 item_id, item_features, item_log_q, negative_item_id, negative_item_features, negative_log_q)

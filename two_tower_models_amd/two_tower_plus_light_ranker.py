@@ -63,6 +63,10 @@ class TwoTowerPlusLightRanker(TwoTowerWithDebiasing):
         if self._sharded():
             raise NotImplementedError(f"TwoTowerPlusLightRanker.{what}: row-sharded models are not supported")
 
+    def _check_cosine_supported(self) -> None:
+        # the ranker's feature m = <u, v> and the MIPS scores it reranks would each need a decision of their own
+        raise NotImplementedError("TwoTowerPlusLightRanker: cosine logits (use_cosine_logits) are not supported")
+
     def _fused_sizes(self) -> bool:
         return ops.light_ranker_supported(self.num_ranker_user_embeddings, self.item_tower_arch.out_features,
                                           self.light_ranker.out_features)
